@@ -11,6 +11,10 @@ shard_bounds(1024, r, N), weights and index replicated) and one RCCL all_gather 
 ids on every rank; the weak-scaling figure (1024 crops per rank) is measured right after and reported
 under "weak".  ``--scaling weak`` makes the weak figure the headline instead.
 
+``--dump-outputs DIR`` (rank 0) writes what the headline's last timed step returned — the top-k scores
+(knn_scores.npy, float32) and ids (knn_ids.npy, float64) of every crop — so that two builds can be
+compared output for output: the inputs are seeded, identical from run to run for the same arguments.
+
 Extra objects on the line:
   roofline      the dominant kernel class, timed live with HIP events recorded on the launch stream
                 INSIDE the timed region by the library's own profiler (effocr_encoder_profile_*):
@@ -39,6 +43,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -87,7 +92,30 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     ap.add_argument("--breakdown", action="store_true", help="also print a per-kernel-class table to stderr")
     ap.add_argument("--verify", action="store_true", help="N>1: check the all-gathered ids against rank 0 encoding every slice itself (exit 1 on mismatch)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (k-NN scores and ids of every crop) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays):
+    """``--dump-outputs``: every array as out_dir/<name>.npy.  The arrays are row-aligned; past DUMP_LIMIT_BYTES in all, a fixed seeded
+    sample of rows is written instead, with the chosen row numbers as sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    keep = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)         # (4096: the .npy headers; + 8: each kept row's number)
+    if keep < rows:
+        sel = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {n: v[sel] for n, v in arrays.items()}
+        arrays["sample_rows"] = sel.astype(np.float64)
+    for n, v in arrays.items():
+        np.save(os.path.join(out_dir, n + ".npy"), np.ascontiguousarray(v))
 
 
 def cpu_baseline(arch, sd, index_cpu, k, target_s):
@@ -251,7 +279,7 @@ def main():
             d, i = knn(emb, k=a.k)
             if world > 1:
                 i = all_gather_rows(i, n_total)
-            return i
+            return d, i
         return step
 
     def fence():
@@ -312,7 +340,14 @@ def main():
     dt, out = timed(step, a.steps)
     clock_main = clock_ghz[0]
     prof = enc.profile_collect() if dom else {}
-    assert tuple(out.shape) == (n_total, a.k)
+    assert tuple(out[1].shape) == (n_total, a.k)
+    if a.dump_outputs:
+        # what the caller of the timed step receives, from its last timed step: the scores and ids of every crop (N>1: the scores are
+        # gathered here, after the timed region, the way the step gathers the ids)
+        d_last, i_last = out
+        if world > 1:
+            d_last = all_gather_rows(d_last, n_total)
+        dump = {"knn_scores": d_last.cpu().numpy().astype(np.float32), "knn_ids": i_last.cpu().numpy().astype(np.float64)}
     other = None
     if world > 1:                                          # the other scaling mode, same run, reported as an extra key
         if scaling == "strong":
@@ -330,7 +365,7 @@ def main():
         # the gathered ids of the STRONG step against rank 0 alone: rank 0 encodes every rank's slice by itself, at that slice's own call
         # size (kernel selection follows the call size, so the per-slice results are reproducible bit for bit), in rank order
         sstep = step if scaling == "strong" else make_step(x_shard, a.batch)
-        got = sstep()
+        got = sstep()[1]
         torch.cuda.synchronize(dev)
         if rank == 0:
             parts = []
@@ -417,6 +452,8 @@ def main():
                 line["extras_error"] = f"{type(e).__name__}: {e}"
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.arch, sd, index_cpu, a.k, a.cpu_seconds)
+        if a.dump_outputs:
+            write_outputs(a.dump_outputs, dump)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

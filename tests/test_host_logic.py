@@ -387,6 +387,39 @@ def test_bench_self_launch_and_scaling_flags():
     assert "torch.distributed.run" in src and "subprocess.call" in src
 
 
+def test_bench_dump_outputs_writer(tmp_path):
+    """bench.py --dump-outputs: float arrays as DIR/<name>.npy, unchanged while they fit; past the size limit a seeded row sample
+    (the same rows every run, their numbers in sample_rows.npy) that stays under the limit; --steps below 1 is refused."""
+    import importlib.util
+    import os
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    rng = np.random.default_rng(1)
+    arrays = {"knn_scores": rng.standard_normal((1000, 10)).astype(np.float32), "knn_ids": rng.integers(0, 10000, (1000, 10)).astype(np.float64)}
+    mod.write_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["knn_ids.npy", "knn_scores.npy"]
+    for n, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{n}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    mod.DUMP_LIMIT_BYTES = 64 << 10
+    for d in ("s1", "s2"):
+        mod.write_outputs(str(tmp_path / d), arrays)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= mod.DUMP_LIMIT_BYTES
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy")
+    assert 0 < len(rows) < 1000 and np.array_equal(rows, np.load(tmp_path / "s2" / "sample_rows.npy"))
+    for n, v in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), v[rows.astype(np.int64)])
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            mod.parse()
+    finally:
+        sys.argv = argv
+
+
 def test_yolov5s_table_and_letterbox_geometry():
     """The layer table has ultralytics' published YOLOv5s (v6) size — 7,235,389 parameters at 80 classes ("YOLOv5s summary:
     270 layers, 7235389 parameters") — and letterbox_geometry is the arithmetic of localizer_engine.py:107-138."""
