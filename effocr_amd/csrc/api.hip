@@ -7,6 +7,7 @@
 
 
 #include <math.h>
+#include <algorithm>
 #include <string.h>
 #include <map>
 #include <memory>
@@ -46,6 +47,9 @@ struct VitLayerOff { size_t ln1w, ln1b, qkvb, projb, ln2w, ln2b, fc1b, fc2b, qkv
                      size_t qkvw_b, projw_b, fc1w_b, fc2w_b, projw_pp, fc2w_pp, projb_p, fc2b_p, qkvw_bv, qkvb_v;
                      size_t qkvw_bf, qkv_s, qkv_c, fc1w_bf, fc1_s, fc1_c; };   // _bf: blocked copy of W . diag(gamma) of the LayerNorm in front; _s: its row sums; _c: b + W beta (gemm3's folded LayerNorm)   // qkvw_bv / qkvb_v: the v rows permuted per 32 (qkvattn.hip)   // _pp / b_p: + rows permuted per 32 (proj fused into the MLP kernel)   // fc2w_pp: k also permuted per 16 (fused MLP)   // *_b: fragment-blocked copies (gemm3), 16-bit modes only
 struct ConvSpec { std::string w, bn; int cin, cout, k, stride, pad; size_t w_off, b_off; };
+// ConvNeXt: per-block / per-stage offsets into the weight blob (channels padded to Cp = multiple of 128, pads zero)
+struct CnxBlockOff { size_t dww, dwb, lnw, lnb, w1, b1, w2, b2, gamma; };   // dww: [49][Cp] fp32; w1: [4C][Cp], w2: [Cp][4C] operands
+struct CnxStageOff { int C, Cp, depth; size_t dslnw, dslnb, dsw, dsb; std::vector<CnxBlockOff> blocks; };   // dsw: [Cp][(kh, kw, c_prev)]
 
 }  // namespace
 }  // namespace effocr
@@ -65,6 +69,10 @@ struct effocr_encoder {
   std::vector<VitLayerOff> layers;
   // resnet18
   std::vector<ConvSpec> convs;      // conv1, then per block conv1, conv2, (downsample)
+  // convnext
+  bool is_cnx = false;
+  std::vector<CnxStageOff> cnx;
+  size_t cnx_stemw = 0, cnx_stemb = 0, cnx_stemlnw = 0, cnx_stemlnb = 0, cnx_headw = 0, cnx_headb = 0;
   size_t wbytes = 0;
   const char* wdev = nullptr;       // device blob after upload
   // optional HIP-event profiler (effocr_encoder_profile_*): one event pair per launch of the
@@ -89,7 +97,7 @@ struct effocr_encoder {
   int use_gemm2 = 1;                // 1: glds-ring K-streaming GEMM for fc2 / patch embed, 0: register-staged gemm.hip
   int panel_rows = 128;             // row-panel height: 128 (1 workgroup/CU) or 64 (2 workgroups/CU)
   int use_panel = 1;                // 0: force the K-streaming GEMM + standalone LayerNorm path (A/B switch)
-  int chunk = 0;                    // crops per internal sub-batch of the ViT forward (0 = whole batch)
+  int chunk = 0;                    // crops per internal sub-batch of the ViT forward (0 = whole batch; ConvNeXt: 0 = cnx_chunk's default)
   int prof_mode = 0;                // 0 off, 1 every class, 2 only prof_only
   std::string prof_only;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
@@ -229,6 +237,55 @@ void build_resnet18(effocr_encoder* e) {
     c.w_off = a.take((size_t)c.cout * K * 4);
     c.b_off = a.take((size_t)c.cout * 4);
   }
+  e->wbytes = a.off;
+}
+
+// ConvNeXt (timm convnext.py key names; DESIGN.md "ConvNeXt-T").  The forward runs in sub-batches; by default as many crops as keep the
+// workspace under CNX_WS_BUDGET (1 GB < 1 GiB), at most CNX_MAX_CHUNK: 192 crops in the 16-bit modes, 124 in fp32 at 224^2.  Measured
+// (fp16, 1024 crops, encoder + k-NN): sub-batches of 32 / 64 / 128 / 192 / 256 crops run at 17.1 / 22.9 / 25.4 / 27.1 / 27.2 k crops/s — the
+// later stages' linears need rows to fill the chip (stage 3 of 32 crops is 1 568 rows: 42 GEMM workgroups on 256 CUs).
+constexpr size_t CNX_WS_BUDGET = (size_t)1000 << 20;
+constexpr int CNX_MAX_CHUNK = 192;
+
+void build_convnext(effocr_encoder* e, const int (&depths)[4], const int (&widths)[4]) {
+  const size_t es = prec_esize(e->prec);
+  add_param(e, "stem.0.weight", {widths[0], 3, 4, 4});
+  add_param(e, "stem.0.bias", {widths[0]});
+  add_param(e, "stem.1.weight", {widths[0]});
+  add_param(e, "stem.1.bias", {widths[0]});
+  Alloc a;
+  e->cnx_stemw = a.take((size_t)48 * 128 * 4);
+  e->cnx_stemb = a.take(128 * 4); e->cnx_stemlnw = a.take(128 * 4); e->cnx_stemlnb = a.take(128 * 4);
+  e->cnx.resize(4);
+  for (int i = 0; i < 4; ++i) {
+    CnxStageOff& st = e->cnx[i];
+    const int C = widths[i], Cp = (int)align_up((size_t)C, 128);
+    st.C = C; st.Cp = Cp; st.depth = depths[i];
+    const std::string p = "stages." + std::to_string(i) + ".";
+    if (i > 0) {
+      const int Cv = widths[i - 1];
+      add_param(e, p + "downsample.0.weight", {Cv}); add_param(e, p + "downsample.0.bias", {Cv});
+      add_param(e, p + "downsample.1.weight", {C, Cv, 2, 2}); add_param(e, p + "downsample.1.bias", {C});
+      st.dslnw = a.take((size_t)Cv * 4); st.dslnb = a.take((size_t)Cv * 4);
+      st.dsw = a.take((size_t)Cp * 4 * Cv * es); st.dsb = a.take((size_t)Cp * 4);
+    }
+    st.blocks.resize(depths[i]);
+    for (int j = 0; j < depths[i]; ++j) {
+      const std::string q = p + "blocks." + std::to_string(j) + ".";
+      add_param(e, q + "gamma", {C});
+      add_param(e, q + "conv_dw.weight", {C, 1, 7, 7}); add_param(e, q + "conv_dw.bias", {C});
+      add_param(e, q + "norm.weight", {C}); add_param(e, q + "norm.bias", {C});
+      add_param(e, q + "mlp.fc1.weight", {4 * C, C}); add_param(e, q + "mlp.fc1.bias", {4 * C});
+      add_param(e, q + "mlp.fc2.weight", {C, 4 * C}); add_param(e, q + "mlp.fc2.bias", {C});
+      CnxBlockOff& L = st.blocks[j];
+      L.dww = a.take((size_t)49 * Cp * 4); L.dwb = a.take((size_t)Cp * 4);
+      L.lnw = a.take((size_t)Cp * 4); L.lnb = a.take((size_t)Cp * 4);
+      L.w1 = a.take((size_t)4 * C * Cp * es); L.b1 = a.take((size_t)4 * C * 4);
+      L.w2 = a.take((size_t)Cp * 4 * C * es); L.b2 = a.take((size_t)Cp * 4); L.gamma = a.take((size_t)Cp * 4);
+    }
+  }
+  add_param(e, "head.norm.weight", {widths[3]}); add_param(e, "head.norm.bias", {widths[3]});
+  e->cnx_headw = a.take((size_t)e->cnx[3].Cp * 4); e->cnx_headb = a.take((size_t)e->cnx[3].Cp * 4);
   e->wbytes = a.off;
 }
 
@@ -377,6 +434,58 @@ void pack_resnet(const effocr_encoder* e, std::vector<char>& blob) {
           }
     }
   }
+}
+
+// ConvNeXt packing: fp32 vectors zero-padded to Cp; dwconv weights tap-major [49][Cp]; fc1 [4C][Cp] with zero columns, fc2 [Cp][4C] with zero
+// rows (the pad channels of the residual stay exactly 0); the downsample conv permuted to [C][kh][kw][C_prev] (the space-to-depth order of
+// cnx_ln_s2d).  The layer scale gamma stays an fp32 vector applied in fc2's epilogue: folded into 16-bit weights, trained values near timm's
+// 1e-6 init would flush to zero in f16.
+void pack_convnext(const effocr_encoder* e, std::vector<char>& blob) {
+  auto padf = [&](size_t off, const std::string& n) { const auto& v = P(e, n); put_f32(blob, off, v.data(), v.size()); };
+  {
+    const auto& w = P(e, "stem.0.weight");
+    const int C0 = e->cnx[0].C;
+    float* d = reinterpret_cast<float*>(blob.data() + e->cnx_stemw);
+    for (int c = 0; c < C0; ++c)
+      for (int k = 0; k < 48; ++k) d[k * 128 + c] = w[(size_t)c * 48 + k];
+    padf(e->cnx_stemb, "stem.0.bias"); padf(e->cnx_stemlnw, "stem.1.weight"); padf(e->cnx_stemlnb, "stem.1.bias");
+  }
+  for (int i = 0; i < 4; ++i) {
+    const CnxStageOff& st = e->cnx[i];
+    const int C = st.C, Cp = st.Cp;
+    const std::string p = "stages." + std::to_string(i) + ".";
+    if (i > 0) {
+      const int Cv = e->cnx[i - 1].C;
+      padf(st.dslnw, p + "downsample.0.weight"); padf(st.dslnb, p + "downsample.0.bias"); padf(st.dsb, p + "downsample.1.bias");
+      const auto& w = P(e, p + "downsample.1.weight");
+      std::vector<float> wp((size_t)Cp * 4 * Cv, 0.f);
+      for (int co = 0; co < C; ++co)
+        for (int ci = 0; ci < Cv; ++ci)
+          for (int kh = 0; kh < 2; ++kh)
+            for (int kw = 0; kw < 2; ++kw) wp[(size_t)co * 4 * Cv + (kh * 2 + kw) * Cv + ci] = w[(((size_t)co * Cv + ci) * 2 + kh) * 2 + kw];
+      put_op(blob, st.dsw, wp.data(), wp.size(), e->prec);
+    }
+    for (int j = 0; j < st.depth; ++j) {
+      const std::string q = p + "blocks." + std::to_string(j) + ".";
+      const CnxBlockOff& L = st.blocks[j];
+      const auto& dw = P(e, q + "conv_dw.weight");
+      float* d = reinterpret_cast<float*>(blob.data() + L.dww);
+      for (int c = 0; c < C; ++c)
+        for (int k = 0; k < 49; ++k) d[(size_t)k * Cp + c] = dw[(size_t)c * 49 + k];
+      padf(L.dwb, q + "conv_dw.bias"); padf(L.lnw, q + "norm.weight"); padf(L.lnb, q + "norm.bias");
+      padf(L.b1, q + "mlp.fc1.bias"); padf(L.b2, q + "mlp.fc2.bias"); padf(L.gamma, q + "gamma");
+      const auto& w1 = P(e, q + "mlp.fc1.weight");
+      std::vector<float> t((size_t)4 * C * Cp, 0.f);
+      for (int n = 0; n < 4 * C; ++n)
+        for (int k = 0; k < C; ++k) t[(size_t)n * Cp + k] = w1[(size_t)n * C + k];
+      put_op(blob, L.w1, t.data(), t.size(), e->prec);
+      const auto& w2 = P(e, q + "mlp.fc2.weight");           // [C][4C] -> [Cp][4C]: the rows past C stay zero
+      t.assign((size_t)Cp * 4 * C, 0.f);
+      memcpy(t.data(), w2.data(), w2.size() * 4);
+      put_op(blob, L.w2, t.data(), t.size(), e->prec);
+    }
+  }
+  padf(e->cnx_headw, "head.norm.weight"); padf(e->cnx_headb, "head.norm.bias");
 }
 
 int prof_class(effocr_encoder* e, const char* name) {
@@ -639,6 +748,81 @@ int vit_forward(effocr_encoder* e, const void* x, int x16, int B, float* emb, in
   return timed(e, "final_cls_norm", 0.0, s, [&] { return final_cls_norm(xs, B, T, D, F(e->off_normw), F(e->off_normb), 1e-6f, l2, blk, emb, status, s); });
 }
 
+// ConvNeXt workspace of one sub-batch of B crops: status word, fp32 residual [tokens][Cp], the operand buffer (dwconv + LayerNorm output =
+// fc1's A, or the downsample's space-to-depth rows) and the hidden [tokens][4C] (fc1 -> fc2).  Stage 0 is the largest for every width table
+// with Cp_i <= 2^i Cp_0 (tokens shrink 4x per stage).
+struct CnxWs { size_t status, x, a, h, total; };
+CnxWs convnext_ws(const effocr_encoder* e, int B) {
+  const size_t es = prec_esize(e->prec);
+  size_t xb = 0, ab = 0, hb = 0;
+  int Hs = e->img / 4;
+  for (int i = 0; i < 4; ++i) {
+    const size_t M = (size_t)B * Hs * Hs, Cp = e->cnx[i].Cp, C = e->cnx[i].C;
+    xb = std::max(xb, M * Cp * 4); ab = std::max(ab, M * Cp * es); hb = std::max(hb, M * 4 * C * es);
+    if (i > 0) ab = std::max(ab, M * 4 * (size_t)e->cnx[i - 1].C * es);
+    Hs /= 2;
+  }
+  Alloc a; CnxWs w;
+  w.status = a.take(256);                   // int32 status word at workspace offset 0 (effocr_encoder_check_status)
+  w.x = a.take(xb); w.a = a.take(ab); w.h = a.take(hb);
+  w.total = a.off;
+  return w;
+}
+
+int cnx_chunk(const effocr_encoder* e, int batch) {
+  int c = e->chunk;
+  if (c <= 0) {
+    const size_t per_crop = convnext_ws(e, 1).total;
+    c = (int)std::min<size_t>(CNX_MAX_CHUNK, std::max<size_t>(1, CNX_WS_BUDGET / per_crop));
+  }
+  return c < batch ? c : batch;
+}
+
+// One sub-batch: stem -> 4 stages of [downsample] + blocks (dwconv+LN -> fc1+GELU -> fc2 x gamma + residual) -> head.  Every kernel's
+// K-reduction order is fixed by the shapes alone (no split-K), so a crop's embedding does not depend on B (batch invariance).
+int convnext_forward(effocr_encoder* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
+  const CnxWs w = convnext_ws(e, B);
+  const char* wb = e->wdev;
+  const int prec = e->prec;
+  auto F = [&](size_t off) { return reinterpret_cast<const float*>(wb + off); };
+  float* xs = reinterpret_cast<float*>(ws + w.x);
+  void* A = ws + w.a; void* hbuf = ws + w.h;
+  int* status = reinterpret_cast<int*>(ws + w.status);
+  int rc;
+  int H = e->img / 4;
+  // 16-bit operands: gemm2 (glds ring) wherever its shape rule holds — it holds for every ConvNeXt linear (N, K multiples of 128); fp32: gemm_nt.
+  // The choice depends on the shape alone, never on M.
+  auto lin = [&](const char* name, const void* X, int K, size_t woff, size_t boff, void* out, int N, int epi, const float* scale, int64_t M) {
+    GemmArgs g{};
+    g.X = X; g.ldx = K; g.W = wb + woff; g.ldw = K; g.bias = F(boff); g.out = out; g.ldo = N; g.M = (int)M; g.N = N; g.K = K;
+    if (epi == EPI_BIAS_SCALE_RESID) { g.resid = xs; g.ldr = N; g.scale = scale; }
+    return timed(e, name, 2.0 * (double)M * N * K, s, [&] {
+      return gemm2_supported(prec, N, K) ? gemm2_nt(prec, epi, g, s) : gemm_nt(prec, epi, g, s); });
+  };
+  if ((rc = timed(e, "cnx_stem", 2.0 * B * H * H * 48.0 * e->cnx[0].C, s, [&] {
+        return cnx_stem(x, B, e->img, F(e->cnx_stemw), F(e->cnx_stemb), F(e->cnx_stemlnw), F(e->cnx_stemlnb), e->cnx[0].C, xs, s); }))) return rc;
+  for (int i = 0; i < 4; ++i) {
+    const CnxStageOff& st = e->cnx[i];
+    const int C = st.C, Cp = st.Cp;
+    if (i > 0) {
+      const int Cv = e->cnx[i - 1].C, Cvp = e->cnx[i - 1].Cp;
+      if ((rc = timed(e, "cnx_ln_s2d", 0.0, s, [&] { return cnx_ln_s2d(prec, xs, B, H, H, Cv, Cvp, F(st.dslnw), F(st.dslnb), A, s); }))) return rc;
+      H /= 2;
+      if ((rc = lin("cnx_downsample", A, 4 * Cv, st.dsw, st.dsb, xs, Cp, EPI_BIAS_F32, nullptr, (int64_t)B * H * H))) return rc;
+    }
+    const int64_t M = (int64_t)B * H * H;
+    for (int j = 0; j < st.depth; ++j) {
+      const CnxBlockOff& L = st.blocks[j];
+      if ((rc = timed(e, "cnx_dwconv_ln", 2.0 * (double)M * 49.0 * C, s, [&] {
+            return cnx_dwconv_ln(prec, xs, B, H, H, C, Cp, F(L.dww), F(L.dwb), F(L.lnw), F(L.lnb), A, s); }))) return rc;
+      if ((rc = lin("cnx_fc1_gelu", A, Cp, L.w1, L.b1, hbuf, 4 * C, EPI_BIAS_GELU, nullptr, M))) return rc;
+      if ((rc = lin("cnx_fc2_scale_resid", hbuf, 4 * C, L.w2, L.b2, xs, Cp, EPI_BIAS_SCALE_RESID, F(L.gamma), M))) return rc;
+    }
+  }
+  const CnxStageOff& last = e->cnx[3];
+  return timed(e, "cnx_head", 0.0, s, [&] { return cnx_head(xs, B, H * H, last.C, last.Cp, F(e->cnx_headw), F(e->cnx_headb), l2, emb, status, s); });
+}
+
 constexpr size_t CONV_SPLIT_BYTES = (size_t)16 << 20;  // split-K scratch of conv2d_nhwc: <= 256 partial tiles of 128 x 128 fp32
 struct ResWs { size_t col, a, b, c, split, total; };
 ResWs resnet_ws(const effocr_encoder* e, int B) {
@@ -732,8 +916,13 @@ int effocr_encoder_create(const char* arch, int img_size, int precision, effocr_
   if (a == "vit_small_patch16_224") e->vit = {384, 12, 6, 1536};
   else if (a == "vit_base_patch16_224") e->vit = {768, 12, 12, 3072};
   else if (a == "vit_tiny_test") e->vit = {128, 2, 2, 512};
-  else if (a != "resnet18") return fail(EFFOCR_EUNSUPPORTED, "encoder_create: unsupported architecture '" + a + "'");
-  if (a == "resnet18") {
+  else if (a != "resnet18" && a != "convnext_tiny") return fail(EFFOCR_EUNSUPPORTED, "encoder_create: unsupported architecture '" + a + "'");
+  if (a == "convnext_tiny") {
+    if (img_size < 32 || img_size % 32) return fail(EFFOCR_EINVAL, "convnext: img_size must be a positive multiple of 32");
+    static const int depths[4] = {3, 3, 9, 3}, widths[4] = {96, 192, 384, 768};
+    e->is_vit = false; e->is_cnx = true; e->D = widths[3];
+    build_convnext(e.get(), depths, widths);
+  } else if (a == "resnet18") {
     if (img_size < 32 || img_size % 32) return fail(EFFOCR_EINVAL, "resnet18: img_size must be a positive multiple of 32");
     e->is_vit = false; e->D = 512;
     e->prec = PREC_FP32;           // the conv path runs exact-fp32 MFMA in every mode
@@ -788,7 +977,7 @@ int effocr_encoder_upload(effocr_encoder_t* enc, void* weights_dev, size_t bytes
   for (const Param& p : enc->params)
     if (!p.set) return fail(EFFOCR_ESTATE, "upload: parameter '" + p.name + "' was never set");
   std::vector<char> blob(enc->wbytes, 0);
-  if (enc->is_vit) pack_vit(enc, blob); else pack_resnet(enc, blob);
+  if (enc->is_vit) pack_vit(enc, blob); else if (enc->is_cnx) pack_convnext(enc, blob); else pack_resnet(enc, blob);
   const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
   if (er != hipSuccess) return fail(EFFOCR_EHIP, std::string("upload: hipMemcpy: ") + hipGetErrorString(er));
   enc->wdev = static_cast<const char*>(weights_dev);
@@ -797,6 +986,7 @@ int effocr_encoder_upload(effocr_encoder_t* enc, void* weights_dev, size_t bytes
 
 size_t effocr_encoder_workspace_bytes(const effocr_encoder_t* enc, int batch) {
   if (!enc || batch <= 0) return 0;
+  if (enc->is_cnx) return convnext_ws(enc, cnx_chunk(enc, batch)).total;
   if (!enc->is_vit) return resnet_ws(enc, batch).total;
   return vit_ws(enc, (enc->chunk > 0 && enc->chunk < batch) ? enc->chunk : batch).total;
 }
@@ -854,6 +1044,22 @@ int effocr_encoder_forward_ex(effocr_encoder_t* enc, const void* x_dev, int x_dt
   if ((int64_t)batch * (enc->is_vit ? enc->T : enc->img * enc->img) >= (int64_t)1 << 30)
     return fail(EFFOCR_EUNSUPPORTED, "forward: batch too large for 32-bit row indices");
   char* ws = static_cast<char*>(workspace_dev);
+  if (enc->is_cnx) {
+    // sub-batches of cnx_chunk crops (default: <= 192, workspace < 1 GB): every kernel reads and writes its own crops' rows only, so the embeddings are
+    // bit-identical for every chunk setting
+    const int chunk = cnx_chunk(enc, batch);
+    const int64_t so = enc->img / 4;
+    if ((int64_t)chunk * so * so * 4 * enc->cnx[0].C >= (int64_t)1 << 31)
+      return fail(EFFOCR_EUNSUPPORTED, "forward: chunk too large for 32-bit GEMM row indices (effocr_encoder_set_chunk)");
+    const size_t img_bytes = (size_t)3 * enc->img * enc->img * 4;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+      const int cb = (batch - b0 < chunk) ? batch - b0 : chunk;
+      const int rc = convnext_forward(enc, reinterpret_cast<const float*>(static_cast<const char*>(x_dev) + (size_t)b0 * img_bytes), cb,
+                                      emb_dev + (size_t)b0 * enc->D, l2_normalize, ws, S(stream));
+      if (rc) return rc;
+    }
+    return EFFOCR_OK;
+  }
   if (!enc->is_vit) return resnet_forward(enc, static_cast<const float*>(x_dev), batch, emb_dev, l2_normalize, ws, S(stream));
   // sub-batches: all activations of `chunk` crops (~1.6 MB per ViT-S crop) stay resident in the
   // 256 MiB Infinity Cache between consecutive kernels instead of round-tripping through HBM
@@ -874,7 +1080,7 @@ int effocr_clock_sample(void* out_dev, void* stream) {
 
 int effocr_encoder_check_status(const effocr_encoder_t* enc, const void* workspace_dev, void* stream) {
   if (!enc || !workspace_dev) return fail(EFFOCR_EINVAL, "check_status: NULL argument");
-  if (!enc->is_vit) return EFFOCR_OK;                     // the CNN path computes in fp32 throughout
+  if (!enc->is_vit && !enc->is_cnx) return EFFOCR_OK;     // the ResNet path computes in fp32 throughout
   int st = 0;
   // on the caller's stream (not the null stream, which would synchronise with every blocking stream of the process)
   hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // VitWs::status = offset 0
@@ -883,7 +1089,8 @@ int effocr_encoder_check_status(const effocr_encoder_t* enc, const void* workspa
   if (er != hipSuccess) return fail(EFFOCR_EHIP, std::string("check_status: ") + hipGetErrorString(er));
   if (st != 0)
     return fail(EFFOCR_EOVERFLOW, enc->prec == PREC_FP16
-                    ? "forward: non-finite embedding — an f16 operand overflowed (|q|, |k|, |v| or an fc1 pre-activation beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint"
+                    ? (enc->is_cnx ? "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm output or a GELU output beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint"
+                                   : "forward: non-finite embedding — an f16 operand overflowed (|q|, |k|, |v| or an fc1 pre-activation beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint")
                     : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
   return EFFOCR_OK;
 }

@@ -128,6 +128,19 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] += rv[i][j][q][e];
   }
+  // EPI_BIAS_SCALE_RESID (ConvNeXt fc2 + layer scale): out = resid + scale * (acc + bias), the residual added AFTER the scale
+  f32x4 sv[2][4], sr[2][2][4];
+  if constexpr (EPI == EPI_BIAS_SCALE_RESID) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + wn * 64 + i * 32 + 8 * q + 4 * half;
+        sv[i][q] = *reinterpret_cast<const f32x4*>(g.scale + n);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) sr[i][j][q] = *reinterpret_cast<const f32x4*>(g.resid + orow[j] * g.ldr + n);
+      }
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     if (!mok[j]) continue;
@@ -147,6 +160,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
             v0 = gelu_erf_fast(v0); v1 = gelu_erf_fast(v1); v2 = gelu_erf_fast(v2); v3 = gelu_erf_fast(v3);
           }
         }
+        if constexpr (EPI == EPI_BIAS_SCALE_RESID) {
+          v0 = fmaf(sv[i][q][0], v0, sr[i][j][q][0]); v1 = fmaf(sv[i][q][1], v1, sr[i][j][q][1]);
+          v2 = fmaf(sv[i][q][2], v2, sr[i][j][q][2]); v3 = fmaf(sv[i][q][3], v3, sr[i][j][q][3]);
+        }
         store4<TO>(out + orow[j] * g.ldo + n, v0, v1, v2, v3);
       }
     }
@@ -161,6 +178,8 @@ int launch_typed(int epi, const GemmArgs& g, hipStream_t s) {
     case EPI_BIAS_GELU:  hipLaunchKernelGGL((gemm_nt_kernel<TA, EPI_BIAS_GELU, TA>), dim3(grid), dim3(256), 0, s, g); break;
     case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm_nt_kernel<TA, EPI_BIAS_RESID, float>), dim3(grid), dim3(256), 0, s, g); break;
     case EPI_PATCH:      hipLaunchKernelGGL((gemm_nt_kernel<TA, EPI_PATCH, float>), dim3(grid), dim3(256), 0, s, g); break;
+    case EPI_BIAS_SCALE_RESID: hipLaunchKernelGGL((gemm_nt_kernel<TA, EPI_BIAS_SCALE_RESID, float>), dim3(grid), dim3(256), 0, s, g); break;
+    case EPI_BIAS_F32:   hipLaunchKernelGGL((gemm_nt_kernel<TA, EPI_BIAS_F32, float>), dim3(grid), dim3(256), 0, s, g); break;
     default: return fail(EFFOCR_EINVAL, "gemm_nt: unknown epilogue");
   }
   return check_launch("gemm_nt");

@@ -108,13 +108,26 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(GemmArgs g) {
     }
   }
   constexpr bool kAdd = (EPI == EPI_BIAS_RESID || EPI == EPI_PATCH);
+  constexpr bool kScale = (EPI == EPI_BIAS_SCALE_RESID);   // ConvNeXt fc2: out = resid + scale * (acc + bias)
   f32x4 bv[2][4];
   f32x4 rv[kAdd ? 2 : 1][2][4];
+  f32x4 sv[kScale ? 2 : 1][4], sr[kScale ? 2 : 1][2][4];
   auto fetch_epilogue = [&]() {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) bv[i][q] = *reinterpret_cast<const f32x4*>(g.bias + n0 + wn * 64 + i * 32 + 8 * q + 4 * half);
+    if constexpr (kScale) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int n = n0 + wn * 64 + i * 32 + 8 * q + 4 * half;
+          sv[i][q] = *reinterpret_cast<const f32x4*>(g.scale + n);
+#pragma unroll
+          for (int j = 0; j < 2; ++j) sr[i][j][q] = *reinterpret_cast<const f32x4*>(g.resid + orow[j] * g.ldr + n);
+        }
+    }
     if constexpr (kAdd) {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -186,6 +199,10 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(GemmArgs g) {
         if constexpr (EPI == EPI_BIAS_GELU) {
           v0 = gelu_erf_fast(v0); v1 = gelu_erf_fast(v1); v2 = gelu_erf_fast(v2); v3 = gelu_erf_fast(v3);
         }
+        if constexpr (kScale) {
+          v0 = fmaf(sv[i][q][0], v0, sr[i][j][q][0]); v1 = fmaf(sv[i][q][1], v1, sr[i][j][q][1]);
+          v2 = fmaf(sv[i][q][2], v2, sr[i][j][q][2]); v3 = fmaf(sv[i][q][3], v3, sr[i][j][q][3]);
+        }
         TO* p = out + orow[j] * g.ldo + n;
         if constexpr (sizeof(TO) == 4) {
           if (g.blk_out) p = reinterpret_cast<TO*>(reinterpret_cast<char*>(out) + blk_off(orow[j], n >> 2, g.N >> 2));
@@ -206,6 +223,8 @@ int launch2(int epi, const GemmArgs& g, hipStream_t s) {
     case EPI_BIAS_GELU:  hipLaunchKernelGGL((gemm2_kernel<E, EPI_BIAS_GELU, E>), dim3(grid), dim3(512), 0, s, g); break;
     case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm2_kernel<E, EPI_BIAS_RESID, float>), dim3(grid), dim3(512), 0, s, g); break;
     case EPI_PATCH:      hipLaunchKernelGGL((gemm2_kernel<E, EPI_PATCH, float>), dim3(grid), dim3(512), 0, s, g); break;
+    case EPI_BIAS_SCALE_RESID: hipLaunchKernelGGL((gemm2_kernel<E, EPI_BIAS_SCALE_RESID, float>), dim3(grid), dim3(512), 0, s, g); break;
+    case EPI_BIAS_F32:   hipLaunchKernelGGL((gemm2_kernel<E, EPI_BIAS_F32, float>), dim3(grid), dim3(512), 0, s, g); break;
     default: return fail(EFFOCR_EINVAL, "gemm2: unknown epilogue");
   }
   return check_launch("gemm2");

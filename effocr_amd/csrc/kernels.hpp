@@ -5,7 +5,9 @@
 namespace effocr {
 
 enum { PREC_BF16 = 0, PREC_FP16 = 1, PREC_FP32 = 2 };
-enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESID = 2, EPI_PATCH = 3 };
+enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESID = 2, EPI_PATCH = 3,
+       EPI_BIAS_SCALE_RESID = 4,        // ConvNeXt fc2: fp32 out = resid + scale[n] * (acc + bias[n])  (layer scale, never folded into W)
+       EPI_BIAS_F32 = 5 };              // ConvNeXt downsample: fp32 out = acc + bias[n] (gemm.hip / gemm2.hip only)
 
 static inline int prec_esize(int prec) { return prec == PREC_FP32 ? 4 : 2; }
 
@@ -29,6 +31,7 @@ struct GemmArgs {
   // lnf_s[n] = sum_k Wblk[n][k]) finishes y = rstd (acc - mean s) + bias in its epilogue — no LayerNorm launch, no fp32 re-read of x.
   float* stats; void* x16;          // producer outputs (NULL: none)
   const float* lnf_stats; const float* lnf_s; int lnf; float lnf_eps;   // consumer inputs
+  const float* scale;               // EPI_BIAS_SCALE_RESID: [N] fp32 layer scale
 };
 
 // gemm.hip
@@ -211,5 +214,17 @@ int nms_yolo_batch(const float* pred, int B, int n, int nc, float conf_thres, fl
                    float* out, int* count, void* ws, size_t ws_bytes, hipStream_t s);
 int nms_yolo(const float* pred, int n, int nc, float conf_thres, float iou_thres, int max_det, int max_nms, float max_wh, int agnostic,
              float* out, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+
+// convnext.hip — the ConvNeXt encoder's own kernels (fp32 channels-last residual stream [tokens][Cp], Cp = channels padded to 128;
+// the pointwise linears are gemm_nt / gemm2_nt).  Every kernel computes a token from that token's inputs alone, in a fixed order.
+// stem: 4x4/s4 conv (wt: [48 taps (c, ky, kx)][128] fp32) + channel LayerNorm over C0 <= 128 -> x [B*(S/4)^2][128] (pad channels 0)
+int cnx_stem(const float* img, int B, int S, const float* wt, const float* bias, const float* lnw, const float* lnb, int C0, float* x, hipStream_t s);
+// depthwise 7x7 (pad 3, bias; w: [49][Cp]) + LayerNorm over the C real channels -> the fc1 operand [B*H*W][Cp] in prec's type (pad channels 0)
+int cnx_dwconv_ln(int prec, const float* x, int B, int H, int W, int C, int Cp, const float* w, const float* bias, const float* lnw,
+                  const float* lnb, void* out, hipStream_t s);
+// downsample LayerNorm written in space-to-depth order: row (b, i, j) of [B*(H/2)*(W/2)][4*C] holds LN(x[b, 2i+kh, 2j+kw]) at (2 kh + kw) * C
+int cnx_ln_s2d(int prec, const float* x, int B, int H, int W, int C, int Cp, const float* lnw, const float* lnb, void* out, hipStream_t s);
+// head: mean over the HW tokens of every image + LayerNorm (+ F.normalize) -> emb [B][C]; ORs 1 into *status on a non-finite embedding
+int cnx_head(const float* x, int B, int HW, int C, int Cp, const float* lnw, const float* lnb, int l2norm, float* emb, int* status, hipStream_t s);
 
 }  // namespace effocr
