@@ -73,6 +73,9 @@ struct effocr_encoder {
   bool is_cnx = false;
   std::vector<CnxStageOff> cnx;
   size_t cnx_stemw = 0, cnx_stemb = 0, cnx_stemlnw = 0, cnx_stemlnb = 0, cnx_headw = 0, cnx_headb = 0;
+  // mobilenetv3_small_050
+  bool is_mnv = false;
+  MnvNet mnv{};
   size_t wbytes = 0;
   const char* wdev = nullptr;       // device blob after upload
   // optional HIP-event profiler (effocr_encoder_profile_*): one event pair per launch of the
@@ -289,6 +292,77 @@ void build_convnext(effocr_encoder* e, const int (&depths)[4], const int (&width
   e->wbytes = a.off;
 }
 
+// MobileNetV3-Small (timm mobilenetv3.py key names; DESIGN.md "MobileNetV3-Small").  The block table of mobilenetv3_small_050 (weights.py
+// builds the same table from timm's arch-def strings; the tests compare the parameter tables).  The forward runs in sub-batches of at most
+// MNV_MAX_CHUNK crops, fewer if the workspace would pass MNV_WS_BUDGET: 512 crops (126 MiB) at 224^2, so a 1024-crop call's activations
+// between kernels stay inside the 256 MiB Infinity Cache.
+constexpr size_t MNV_WS_BUDGET = (size_t)128 << 20;
+constexpr int MNV_MAX_CHUNK = 512;
+struct MnvRow { const char* key; int cin, mid, cout, k, stride, se, hs, res; };
+const MnvRow MNV_050[MNV_NBLK] = {
+    {"blocks.0.0", 16, 16, 8, 3, 2, 8, 0, 0},     // depthwise-separable: conv_dw, bn1, se, conv_pw, bn2
+    {"blocks.1.0", 8, 40, 16, 3, 2, 0, 0, 0},     {"blocks.1.1", 16, 56, 16, 3, 1, 0, 0, 1},
+    {"blocks.2.0", 16, 64, 24, 5, 2, 16, 1, 0},   {"blocks.2.1", 24, 144, 24, 5, 1, 40, 1, 1}, {"blocks.2.2", 24, 144, 24, 5, 1, 40, 1, 1},
+    {"blocks.3.0", 24, 72, 24, 5, 1, 24, 1, 1},   {"blocks.3.1", 24, 72, 24, 5, 1, 24, 1, 1},
+    {"blocks.4.0", 24, 144, 48, 5, 2, 40, 1, 0},  {"blocks.4.1", 48, 288, 48, 5, 1, 72, 1, 1}, {"blocks.4.2", 48, 288, 48, 5, 1, 72, 1, 1},
+};
+
+int build_mobilenetv3(effocr_encoder* e) {
+  const size_t es = prec_esize(e->prec);
+  MnvNet& n = e->mnv;
+  n.S = e->img; n.stem_c = 16; n.cn_c = 288; n.nf = 1024;
+  Alloc a;
+  auto bn = [&](const std::string& p, int c) {
+    for (const char* leaf : {"weight", "bias", "running_mean", "running_var"}) add_param(e, p + "." + leaf, {c});
+  };
+  auto se = [&](const std::string& p, int c, int r) {
+    add_param(e, p + ".se.conv_reduce.weight", {r, c, 1, 1}); add_param(e, p + ".se.conv_reduce.bias", {r});
+    add_param(e, p + ".se.conv_expand.weight", {c, r, 1, 1}); add_param(e, p + ".se.conv_expand.bias", {c});
+  };
+  auto pw = [&](int N, int K) { MnvConv c; c.w = (uint32_t)a.take((size_t)N * K * es); c.b = (uint32_t)a.take((size_t)N * 4); return c; };
+  auto f32 = [&](size_t wn, size_t bn_) { MnvConv c; c.w = (uint32_t)a.take(wn * 4); c.b = (uint32_t)a.take(bn_ * 4); return c; };
+  add_param(e, "conv_stem.weight", {16, 3, 3, 3});
+  bn("bn1", 16);
+  n.stem = f32(16 * 27, 16);
+  int H = e->img / 8;                                   // the S/8 map feeds mnv3_tail
+  for (int i = 0; i < MNV_NBLK; ++i) {
+    const MnvRow& r = MNV_050[i];
+    MnvBlock& b = n.blk[i];
+    b.cin = r.cin; b.mid = r.mid; b.cout = r.cout; b.k = r.k; b.stride = r.stride; b.se = r.se; b.hs = r.hs; b.res = r.res; b.cg = r.mid;
+    const std::string p = r.key;
+    if (i == 0) {
+      add_param(e, p + ".conv_dw.weight", {r.cin, 1, r.k, r.k}); bn(p + ".bn1", r.cin);
+      se(p, r.cin, r.se);
+      add_param(e, p + ".conv_pw.weight", {r.cout, r.cin, 1, 1}); bn(p + ".bn2", r.cout);
+    } else {
+      add_param(e, p + ".conv_pw.weight", {r.mid, r.cin, 1, 1}); bn(p + ".bn1", r.mid);
+      add_param(e, p + ".conv_dw.weight", {r.mid, 1, r.k, r.k}); bn(p + ".bn2", r.mid);
+      if (r.se) se(p, r.mid, r.se);
+      add_param(e, p + ".conv_pwl.weight", {r.cout, r.mid, 1, 1}); bn(p + ".bn3", r.cout);
+      b.pw = pw(r.mid, r.cin);
+    }
+    b.dw = f32((size_t)r.k * r.k * r.mid, r.mid);
+    if (r.se) { b.ser = f32((size_t)r.se * r.mid, r.se); b.see = f32((size_t)r.mid * r.se, r.mid); }
+    b.pwl = pw(r.cout, r.mid);
+    if (i >= 3) {                                       // mnv3_tail: the largest expansion channel group that fits the LDS arena
+      const int Ho = (H - 1) / r.stride + 1, fixed = H * H * r.cin + Ho * Ho * r.mid;
+      b.cg = 0;
+      for (int d = r.mid; d >= 1; --d)
+        if (r.mid % d == 0 && fixed + H * H * d <= MNV_TAIL_LDS_FLOATS) { b.cg = d; break; }
+      if (b.cg == 0) return fail(EFFOCR_EUNSUPPORTED, "mobilenetv3: block " + p + " does not fit the LDS arena");
+      H = Ho;
+    }
+  }
+  add_param(e, "blocks.5.0.conv.weight", {288, 48, 1, 1}); bn("blocks.5.0.bn1", 288);
+  n.cn = pw(288, 48);
+  if (H * H * (48 + 288) > MNV_TAIL_LDS_FLOATS) return fail(EFFOCR_EUNSUPPORTED, "mobilenetv3: blocks.5.0 does not fit the LDS arena");
+  add_param(e, "conv_head.weight", {1024, 288, 1, 1}); add_param(e, "conv_head.bias", {1024});
+  n.head = pw(1024, 288);
+  e->wbytes = a.off;
+  if (e->wbytes >= ((size_t)1 << 32)) return fail(EFFOCR_EUNSUPPORTED, "mobilenetv3: weight blob too large");
+  return EFFOCR_OK;
+}
+
 uint16_t f32_to_bf16(float f) {
   uint32_t u; memcpy(&u, &f, 4);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
@@ -486,6 +560,58 @@ void pack_convnext(const effocr_encoder* e, std::vector<char>& blob) {
     }
   }
   padf(e->cnx_headw, "head.norm.weight"); padf(e->cnx_headb, "head.norm.bias");
+}
+
+// MobileNetV3 packing: every BatchNorm folded into the conv in front of it in fp32 (w' = w g / sqrt(v + eps), b' = beta - m g / sqrt(v + eps));
+// pointwise weights [N][K] then rounded to the operand type; depthwise weights tap-major [k*k][C] fp32; SE convs fp32 as they are.
+void pack_mobilenetv3(const effocr_encoder* e, std::vector<char>& blob) {
+  const MnvNet& n = e->mnv;
+  auto fold = [&](const std::string& w, const std::string& bn, std::vector<float>& wf, std::vector<float>& bf) {
+    const auto& W = P(e, w);
+    const auto& g = P(e, bn + ".weight"); const auto& be = P(e, bn + ".bias");
+    const auto& m = P(e, bn + ".running_mean"); const auto& v = P(e, bn + ".running_var");
+    const size_t C = g.size(), per = W.size() / C;
+    wf.resize(W.size()); bf.resize(C);
+    for (size_t c = 0; c < C; ++c) {
+      const float sc = g[c] / sqrtf(v[c] + 1e-5f);
+      for (size_t k = 0; k < per; ++k) wf[c * per + k] = W[c * per + k] * sc;
+      bf[c] = be[c] - m[c] * sc;
+    }
+  };
+  std::vector<float> wf, bf;
+  auto put_pw = [&](const MnvConv& c, const std::string& w, const std::string& bn) {
+    fold(w, bn, wf, bf); put_op(blob, c.w, wf.data(), wf.size(), e->prec); put_f32(blob, c.b, bf.data(), bf.size());
+  };
+  auto put_dw = [&](const MnvConv& c, const std::string& w, const std::string& bn, int C, int k) {
+    fold(w, bn, wf, bf);
+    float* d = reinterpret_cast<float*>(blob.data() + c.w);
+    for (int ch = 0; ch < C; ++ch)
+      for (int t = 0; t < k * k; ++t) d[(size_t)t * C + ch] = wf[(size_t)ch * k * k + t];
+    put_f32(blob, c.b, bf.data(), bf.size());
+  };
+  auto put_plain = [&](const MnvConv& c, const std::string& p) {
+    const auto& w = P(e, p + ".weight"); const auto& b = P(e, p + ".bias");
+    put_f32(blob, c.w, w.data(), w.size()); put_f32(blob, c.b, b.data(), b.size());
+  };
+  fold("conv_stem.weight", "bn1", wf, bf);
+  put_f32(blob, n.stem.w, wf.data(), wf.size()); put_f32(blob, n.stem.b, bf.data(), bf.size());
+  for (int i = 0; i < MNV_NBLK; ++i) {
+    const MnvRow& r = MNV_050[i];
+    const MnvBlock& b = n.blk[i];
+    const std::string p = r.key;
+    if (i == 0) {
+      put_dw(b.dw, p + ".conv_dw.weight", p + ".bn1", r.cin, r.k);
+      put_pw(b.pwl, p + ".conv_pw.weight", p + ".bn2");
+    } else {
+      put_pw(b.pw, p + ".conv_pw.weight", p + ".bn1");
+      put_dw(b.dw, p + ".conv_dw.weight", p + ".bn2", r.mid, r.k);
+      put_pw(b.pwl, p + ".conv_pwl.weight", p + ".bn3");
+    }
+    if (r.se) { put_plain(b.ser, p + ".se.conv_reduce"); put_plain(b.see, p + ".se.conv_expand"); }
+  }
+  put_pw(n.cn, "blocks.5.0.conv.weight", "blocks.5.0.bn1");
+  const auto& hw = P(e, "conv_head.weight"); const auto& hb = P(e, "conv_head.bias");
+  put_op(blob, n.head.w, hw.data(), hw.size(), e->prec); put_f32(blob, n.head.b, hb.data(), hb.size());
 }
 
 int prof_class(effocr_encoder* e, const char* name) {
@@ -823,6 +949,65 @@ int convnext_forward(effocr_encoder* e, const float* x, int B, float* emb, int l
   return timed(e, "cnx_head", 0.0, s, [&] { return cnx_head(xs, B, H * H, last.C, last.Cp, F(e->cnx_headw), F(e->cnx_headb), l2, emb, status, s); });
 }
 
+// MobileNetV3 workspace of one sub-batch of B crops: status word, the S/4 map of blocks.0.0's depthwise output [B][S/4][S/4][16] and its
+// per-tile channel sums, the S/8 map after blocks.1.1 [B][S/8][S/8][16], the pooled vectors [B][288].  All fp32.
+struct MnvWs { size_t status, t0, part, t1, pooled, total; };
+MnvWs mnv3_ws(const effocr_encoder* e, int B) {
+  const size_t S4 = e->img / 4, S8 = e->img / 8;
+  Alloc a; MnvWs w;
+  w.status = a.take(256);
+  w.t0 = a.take((size_t)B * S4 * S4 * 16 * 4);
+  w.part = a.take((size_t)B * mnv3_tiles1(e->img) * 16 * 4);
+  w.t1 = a.take((size_t)B * S8 * S8 * 16 * 4);
+  w.pooled = a.take((size_t)B * e->mnv.cn_c * 4);
+  w.total = a.off;
+  return w;
+}
+
+int mnv3_chunk(const effocr_encoder* e, int batch) {
+  int c = e->chunk;
+  if (c <= 0) c = (int)std::min<size_t>(MNV_MAX_CHUNK, std::max<size_t>(1, MNV_WS_BUDGET / mnv3_ws(e, 1).total));
+  return c < batch ? c : batch;
+}
+
+// MACs per crop of each kernel (the profiler's algorithmic FLOPs are 2x these)
+struct MnvMacs { double stem_ds, stage1, tail, head; };
+MnvMacs mnv3_macs(const effocr_encoder* e) {
+  const MnvNet& n = e->mnv;
+  const double S2 = e->img / 2, S4 = e->img / 4;
+  MnvMacs m{};
+  m.stem_ds = S2 * S2 * 16 * 27 + S4 * S4 * 16 * 9;
+  double H = S4;                                        // blocks.0.0's depthwise conv (S/2 -> S/4) is counted in mnv3_stem_ds
+  m.stage1 = H * H * n.blk[0].cin * n.blk[0].cout + 2.0 * n.blk[0].cin * n.blk[0].se;
+  for (int i = 1; i < MNV_NBLK; ++i) {
+    const MnvBlock& b = n.blk[i];
+    const double Ho = std::floor((H - 1) / b.stride) + 1;
+    (i < 3 ? m.stage1 : m.tail) += H * H * b.cin * b.mid + Ho * Ho * b.mid * (b.k * b.k + b.cout) + 2.0 * b.mid * b.se;
+    H = Ho;
+  }
+  m.tail += H * H * n.blk[MNV_NBLK - 1].cout * n.cn_c;
+  m.head = (double)n.cn_c * n.nf;
+  return m;
+}
+
+// One sub-batch: mnv3_stem_ds -> mnv3_stage1 -> mnv3_tail -> mnv3_head.  Each kernel computes a crop from that crop's data alone, in an
+// order fixed by the shapes (batch invariance).
+int mnv3_forward(effocr_encoder* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
+  const MnvWs w = mnv3_ws(e, B);
+  const MnvMacs m = mnv3_macs(e);
+  const char* wb = e->wdev;
+  float* t0 = reinterpret_cast<float*>(ws + w.t0);
+  float* part = reinterpret_cast<float*>(ws + w.part);
+  float* t1 = reinterpret_cast<float*>(ws + w.t1);
+  float* pooled = reinterpret_cast<float*>(ws + w.pooled);
+  int* status = reinterpret_cast<int*>(ws + w.status);
+  int rc;
+  if ((rc = timed(e, "mnv3_stem_ds", 2.0 * B * m.stem_ds, s, [&] { return mnv3_stem_ds(e->prec, x, B, wb, e->mnv, t0, part, s); }))) return rc;
+  if ((rc = timed(e, "mnv3_stage1", 2.0 * B * m.stage1, s, [&] { return mnv3_stage1(e->prec, t0, part, B, wb, e->mnv, t1, s); }))) return rc;
+  if ((rc = timed(e, "mnv3_tail", 2.0 * B * m.tail, s, [&] { return mnv3_tail(e->prec, t1, B, wb, e->mnv, pooled, s); }))) return rc;
+  return timed(e, "mnv3_head", 2.0 * B * m.head, s, [&] { return mnv3_head(e->prec, pooled, B, wb, e->mnv, l2, emb, status, s); });
+}
+
 constexpr size_t CONV_SPLIT_BYTES = (size_t)16 << 20;  // split-K scratch of conv2d_nhwc: <= 256 partial tiles of 128 x 128 fp32
 struct ResWs { size_t col, a, b, c, split, total; };
 ResWs resnet_ws(const effocr_encoder* e, int B) {
@@ -916,8 +1101,15 @@ int effocr_encoder_create(const char* arch, int img_size, int precision, effocr_
   if (a == "vit_small_patch16_224") e->vit = {384, 12, 6, 1536};
   else if (a == "vit_base_patch16_224") e->vit = {768, 12, 12, 3072};
   else if (a == "vit_tiny_test") e->vit = {128, 2, 2, 512};
-  else if (a != "resnet18" && a != "convnext_tiny") return fail(EFFOCR_EUNSUPPORTED, "encoder_create: unsupported architecture '" + a + "'");
-  if (a == "convnext_tiny") {
+  else if (a != "resnet18" && a != "convnext_tiny" && a != "mobilenetv3_small_050")
+    return fail(EFFOCR_EUNSUPPORTED, "encoder_create: unsupported architecture '" + a + "'");
+  if (a == "mobilenetv3_small_050") {
+    if (img_size < 32 || img_size > 224 || img_size % 32)
+      return fail(EFFOCR_EINVAL, "mobilenetv3: img_size must be a multiple of 32 in [32, 224]");
+    e->is_vit = false; e->is_mnv = true; e->D = 1024;
+    const int rc = build_mobilenetv3(e.get());
+    if (rc) return rc;
+  } else if (a == "convnext_tiny") {
     if (img_size < 32 || img_size % 32) return fail(EFFOCR_EINVAL, "convnext: img_size must be a positive multiple of 32");
     static const int depths[4] = {3, 3, 9, 3}, widths[4] = {96, 192, 384, 768};
     e->is_vit = false; e->is_cnx = true; e->D = widths[3];
@@ -977,7 +1169,8 @@ int effocr_encoder_upload(effocr_encoder_t* enc, void* weights_dev, size_t bytes
   for (const Param& p : enc->params)
     if (!p.set) return fail(EFFOCR_ESTATE, "upload: parameter '" + p.name + "' was never set");
   std::vector<char> blob(enc->wbytes, 0);
-  if (enc->is_vit) pack_vit(enc, blob); else if (enc->is_cnx) pack_convnext(enc, blob); else pack_resnet(enc, blob);
+  if (enc->is_vit) pack_vit(enc, blob); else if (enc->is_cnx) pack_convnext(enc, blob); else if (enc->is_mnv) pack_mobilenetv3(enc, blob);
+  else pack_resnet(enc, blob);
   const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
   if (er != hipSuccess) return fail(EFFOCR_EHIP, std::string("upload: hipMemcpy: ") + hipGetErrorString(er));
   enc->wdev = static_cast<const char*>(weights_dev);
@@ -987,6 +1180,7 @@ int effocr_encoder_upload(effocr_encoder_t* enc, void* weights_dev, size_t bytes
 size_t effocr_encoder_workspace_bytes(const effocr_encoder_t* enc, int batch) {
   if (!enc || batch <= 0) return 0;
   if (enc->is_cnx) return convnext_ws(enc, cnx_chunk(enc, batch)).total;
+  if (enc->is_mnv) return mnv3_ws(enc, mnv3_chunk(enc, batch)).total;
   if (!enc->is_vit) return resnet_ws(enc, batch).total;
   return vit_ws(enc, (enc->chunk > 0 && enc->chunk < batch) ? enc->chunk : batch).total;
 }
@@ -1060,6 +1254,18 @@ int effocr_encoder_forward_ex(effocr_encoder_t* enc, const void* x_dev, int x_dt
     }
     return EFFOCR_OK;
   }
+  if (enc->is_mnv) {
+    // sub-batches of mnv3_chunk crops (default: <= 512, workspace <= 128 MiB); every kernel reads and writes its own crops' data only
+    const int chunk = mnv3_chunk(enc, batch);
+    const size_t img_bytes = (size_t)3 * enc->img * enc->img * 4;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+      const int cb = (batch - b0 < chunk) ? batch - b0 : chunk;
+      const int rc = mnv3_forward(enc, reinterpret_cast<const float*>(static_cast<const char*>(x_dev) + (size_t)b0 * img_bytes), cb,
+                                  emb_dev + (size_t)b0 * enc->D, l2_normalize, ws, S(stream));
+      if (rc) return rc;
+    }
+    return EFFOCR_OK;
+  }
   if (!enc->is_vit) return resnet_forward(enc, static_cast<const float*>(x_dev), batch, emb_dev, l2_normalize, ws, S(stream));
   // sub-batches: all activations of `chunk` crops (~1.6 MB per ViT-S crop) stay resident in the
   // 256 MiB Infinity Cache between consecutive kernels instead of round-tripping through HBM
@@ -1080,7 +1286,7 @@ int effocr_clock_sample(void* out_dev, void* stream) {
 
 int effocr_encoder_check_status(const effocr_encoder_t* enc, const void* workspace_dev, void* stream) {
   if (!enc || !workspace_dev) return fail(EFFOCR_EINVAL, "check_status: NULL argument");
-  if (!enc->is_vit && !enc->is_cnx) return EFFOCR_OK;     // the ResNet path computes in fp32 throughout
+  if (!enc->is_vit && !enc->is_cnx && !enc->is_mnv) return EFFOCR_OK;     // the ResNet path computes in fp32 throughout
   int st = 0;
   // on the caller's stream (not the null stream, which would synchronise with every blocking stream of the process)
   hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // VitWs::status = offset 0
@@ -1089,7 +1295,8 @@ int effocr_encoder_check_status(const effocr_encoder_t* enc, const void* workspa
   if (er != hipSuccess) return fail(EFFOCR_EHIP, std::string("check_status: ") + hipGetErrorString(er));
   if (st != 0)
     return fail(EFFOCR_EOVERFLOW, enc->prec == PREC_FP16
-                    ? (enc->is_cnx ? "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm output or a GELU output beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint"
+                    ? (enc->is_mnv ? "forward: non-finite embedding — an f16 operand overflowed (an activation beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint"
+                       : enc->is_cnx ? "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm output or a GELU output beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint"
                                    : "forward: non-finite embedding — an f16 operand overflowed (|q|, |k|, |v| or an fc1 pre-activation beyond 65504) or the input was not finite; use precision bf16 or fp32 for this checkpoint")
                     : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
   return EFFOCR_OK;

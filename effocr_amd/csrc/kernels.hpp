@@ -227,4 +227,27 @@ int cnx_ln_s2d(int prec, const float* x, int B, int H, int W, int C, int Cp, con
 // head: mean over the HW tokens of every image + LayerNorm (+ F.normalize) -> emb [B][C]; ORs 1 into *status on a non-finite embedding
 int cnx_head(const float* x, int B, int HW, int C, int Cp, const float* lnw, const float* lnb, int l2norm, float* emb, int* status, hipStream_t s);
 
+// mobilenetv3.hip — the MobileNetV3-Small encoder (timm mobilenetv3_small_050; api.hip: mnv3_forward).  BN is folded into every conv on
+// the host.  Offsets are byte offsets into the packed weight blob; pointwise weights [N][K] are in the handle's operand type, everything
+// else fp32 (depthwise [k*k][C], SE [out][in], stem [16][27]).  Every kernel computes one crop from that crop's inputs alone, in a fixed
+// order, so a crop's embedding does not depend on the call size or the chunking.
+struct MnvConv { uint32_t w, b; };
+struct MnvBlock { int cin, mid, cout, k, stride, se, hs, res, cg; MnvConv pw, dw, ser, see, pwl; };   // ds block: dw, ser/see, pwl = conv_pw
+constexpr int MNV_NBLK = 11;
+struct MnvNet { int S, stem_c, cn_c, nf; MnvConv stem, cn, head; MnvBlock blk[MNV_NBLK]; };
+constexpr int MNV_T1 = 8, MNV_T2 = 8;              // output tile edge of mnv3_stem_ds (S/4 map) and mnv3_stage1 (S/8 map)
+constexpr int MNV_TAIL_LDS_FLOATS = 39680;         // arena of mnv3_tail (blocks 2.0 .. 5.0 of one crop at 224^2)
+__host__ __device__ static inline int mnv3_tiles1(int S) { const int n = (S / 4 + MNV_T1 - 1) / MNV_T1; return n * n; }
+__host__ __device__ static inline int mnv3_tiles2(int S) { const int n = (S / 8 + MNV_T2 - 1) / MNV_T2; return n * n; }
+// stem 3x3/s2 + BN + hard-swish fused with blocks.0.0's depthwise 3x3/s2 + BN + ReLU (stem halos recomputed per tile):
+// t0 [B][S/4][S/4][16] fp32, part [B][tiles1][16] fp32 = each tile's channel sums (SE squeeze, summed later in tile order)
+int mnv3_stem_ds(int prec, const float* img, int B, const char* wb, const MnvNet& net, float* t0, float* part, hipStream_t s);
+// blocks.0.0's SE gate + conv_pw, then blocks.1.0 and blocks.1.1 per 8x8 tile of the S/8 map (halos recomputed) -> t1 [B][S/8][S/8][16]
+int mnv3_stage1(int prec, const float* t0, const float* part, int B, const char* wb, const MnvNet& net, float* t1, hipStream_t s);
+// blocks.2.0 .. blocks.5.0 + global average pool of one crop per workgroup, all in LDS -> pooled [B][cn_c] fp32
+int mnv3_tail(int prec, const float* t1, int B, const char* wb, const MnvNet& net, float* pooled, hipStream_t s);
+// conv_head over the pooled vectors (batched GEMM, 16 crops per workgroup) + bias + hard-swish (+ F.normalize) -> emb [B][nf];
+// ORs 1 into *status on a non-finite embedding
+int mnv3_head(int prec, const float* pooled, int B, const char* wb, const MnvNet& net, int l2norm, float* emb, int* status, hipStream_t s);
+
 }  // namespace effocr

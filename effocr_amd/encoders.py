@@ -73,8 +73,8 @@ class HipEncoder:
             pass
 
     def set_chunk(self, crops_per_chunk):
-        """Internal sub-batch size of the ViT / ConvNeXt forward (ViT: 0 = whole batch; ConvNeXt: 0 = the library's default, a
-        workspace under 1 GB); see effocr_encoder_set_chunk."""
+        """Internal sub-batch size of the ViT / ConvNeXt / MobileNetV3 forward (ViT: 0 = whole batch; ConvNeXt: 0 = the library's
+        default, a workspace under 1 GB; MobileNetV3: 0 = at most 512 crops, a workspace under 128 MiB); see effocr_encoder_set_chunk."""
         _lib.check(self._L.effocr_encoder_set_chunk(self._h, int(crops_per_chunk)), "effocr_encoder_set_chunk", self._L)
         # (the per-stream workspaces stay: they are grow-only scratch, re-sized by the next forward if it needs more, and their first
         # word is the sticky status — dropping them would drop an unchecked overflow)
@@ -89,7 +89,8 @@ class HipEncoder:
     def crop_dtype(self):
         """Element type a crop producer on the device should hand over (PairedTransform.boxes_batch(dtype=...), SURVEY f-2): the
         ViT encoders' own 16-bit operand type — the patch embedding rounds fp32 crops to it anyway, so the embeddings are
-        bit-identical and half the bytes move — float32 for the fp32 mode and the CNNs (resnet18, convnext_tiny)."""
+        bit-identical and half the bytes move — float32 for the fp32 mode and the CNNs (resnet18, convnext_tiny,
+        mobilenetv3_small_050), whose first layer is an fp32 conv in every mode."""
         if self.arch.startswith("vit") and self.precision in _CROP_DTYPE:
             return _CROP_DTYPE[self.precision]
         return torch.float32
@@ -272,8 +273,8 @@ class HipEncoder:
 def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size=224):
     """Drop-in for models/encoders.py:50 ``AutoEncoderFactory(backend, modelpath)``.
 
-    Only the ``"timm"`` backend with the architectures BASELINE.json names and ``convnext_tiny`` (recommended by the reference
-    README for ``--auto_model_timm``) is implemented (the "hf" branch and XcitDinoEncoder are out of scope); anything else raises
+    Only the ``"timm"`` backend with the architectures BASELINE.json names, ``convnext_tiny`` and ``mobilenetv3_small_050``
+    (recommended by the reference README for ``--auto_model_timm``) is implemented (the "hf" branch and XcitDinoEncoder are out of scope); anything else raises
     NotImplementedError exactly like the reference's ``else`` branch (encoders.py:93-95).
     ``precision`` / ``img_size`` are extensions with reference-compatible defaults.
     """

@@ -13,9 +13,15 @@ ConvNeXt key names follow timm's ``convnext.py`` (``stem.0`` / ``stem.1``, ``sta
 project, so those names could not be checked against timm itself here; the architecture and the parameter
 shapes are pinned against ``transformers.ConvNextModel`` by the tests (tests/test_convnext_host.py), the same
 caveat that applies to the faiss index layout of knn.py.
+
+MobileNetV3 (``mobilenetv3_small_050``) is described by timm's arch-def strings and a channel multiplier
+(``mobilenetv3_blocks``), from which the key names and shapes follow (``conv_stem``, ``bn1``,
+``blocks.i.j.{conv_pw,bn1,conv_dw,bn2,se.conv_reduce,se.conv_expand,conv_pwl,bn3}``, ``conv_head``); the
+builder is pinned by the parameter counts of three widths (tests/test_mobilenetv3_host.py).
 """
 from collections import OrderedDict
 import math
+import re
 import torch
 
 VIT_CFG = {
@@ -29,7 +35,69 @@ CONVNEXT_CFG = {
     # name: (depths, widths) — timm convnext.py; convnext_small would be ((3, 3, 27, 3), (96, 192, 384, 768))
     "convnext_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
 }
+MOBILENETV3_CFG = {
+    # name: channel multiplier — timm mobilenetv3.py _gen_mobilenet_v3 ("small"); only _050 has kernels, the other two widths pin the builder
+    "mobilenetv3_small_050": 0.5,
+    "mobilenetv3_small_075": 0.75,
+    "mobilenetv3_small_100": 1.0,
+}
+MOBILENETV3_ARCH_DEF = (
+    # timm's arch-def strings for MobileNetV3-Small: one list per stage; "nre" = ReLU, otherwise hard-swish
+    ("ds_r1_k3_s2_e1_c16_se0.25_nre",),
+    ("ir_r1_k3_s2_e4.5_c24_nre", "ir_r1_k3_s1_e3.67_c24_nre"),
+    ("ir_r1_k5_s2_e4_c40_se0.25", "ir_r2_k5_s1_e6_c40_se0.25"),
+    ("ir_r2_k5_s1_e3_c48_se0.25",),
+    ("ir_r3_k5_s2_e6_c96_se0.25",),
+    ("cn_r1_k1_s1_c576",),
+)
+MOBILENETV3_FEATURES = 1024           # conv_head width (not scaled by the multiplier)
 PATCH = 16
+
+
+def make_divisible(v, divisor=8, min_value=None, round_limit=0.9):
+    """timm layers/helpers.py make_divisible."""
+    min_value = min_value or divisor
+    new_v = max(min_value, int(v + divisor / 2) // divisor * divisor)
+    if new_v < round_limit * v:
+        new_v += divisor
+    return new_v
+
+
+def mobilenetv3_blocks(arch):
+    """(stem channels, [block dicts], head width) of a MobileNetV3-Small width, built from MOBILENETV3_ARCH_DEF the way timm's
+    _efficientnet_builder does.  A block dict has: key (e.g. "blocks.2.1"), type ("ds" | "ir" | "cn"), cin, mid, cout, k, stride,
+    se (SE width, 0 = none), hs (hard-swish, else ReLU), res (residual)."""
+    mult = MOBILENETV3_CFG[arch]
+    stem = 16 if mult < 0.75 else make_divisible(16 * mult)   # fix_stem = multiplier < 0.75
+    blocks, cin = [], stem
+    for si, stage in enumerate(MOBILENETV3_ARCH_DEF):
+        bi = 0
+        for bs in stage:
+            ops = bs.split("_")
+            opt = {}
+            for o in ops[1:]:
+                m = re.match(r"([a-z]+)([0-9.]*)$", o)
+                opt[m.group(1)] = m.group(2)
+            for r in range(int(opt["r"])):
+                cout = make_divisible(int(opt["c"]) * mult)
+                stride = int(opt["s"]) if r == 0 else 1
+                k = int(opt["k"])
+                if ops[0] == "ds":
+                    mid = cin
+                elif ops[0] == "ir":
+                    mid = make_divisible(cin * float(opt["e"]))
+                else:
+                    mid = cout
+                se = make_divisible(mid * float(opt["se"])) if "se" in opt else 0
+                blocks.append(dict(key=f"blocks.{si}.{bi}", type=ops[0], cin=cin, mid=mid, cout=cout, k=k, stride=stride, se=se,
+                                   hs="nre" not in opt, res=(ops[0] != "cn" and stride == 1 and cin == cout)))
+                cin = cout
+                bi += 1
+    return stem, blocks, MOBILENETV3_FEATURES
+
+
+def is_mobilenetv3(arch):
+    return arch in MOBILENETV3_CFG
 
 
 def is_vit(arch):
@@ -43,6 +111,8 @@ def embed_dim(arch):
         return RESNET_CFG[arch][1][-1]
     if arch in CONVNEXT_CFG:
         return CONVNEXT_CFG[arch][1][-1]
+    if arch in MOBILENETV3_CFG:
+        return MOBILENETV3_FEATURES
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -129,7 +199,64 @@ def param_shapes(arch, img_size=224):
         s["head.norm.weight"] = (widths[-1],)
         s["head.norm.bias"] = (widths[-1],)
         return s
+    if arch in MOBILENETV3_CFG:
+        return _mobilenetv3_shapes(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _mobilenetv3_shapes(arch, num_classes=0):
+    """timm's state-dict order: a module's own parameters, then its children's; BN with running statistics (num_batches_tracked
+    left out, as for the other CNNs)."""
+    s = OrderedDict()
+
+    def bn(p, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{p}.{leaf}"] = (c,)
+
+    def se(p, c, r):
+        s[p + ".se.conv_reduce.weight"] = (r, c, 1, 1)
+        s[p + ".se.conv_reduce.bias"] = (r,)
+        s[p + ".se.conv_expand.weight"] = (c, r, 1, 1)
+        s[p + ".se.conv_expand.bias"] = (c,)
+    stem, blocks, nf = mobilenetv3_blocks(arch)
+    s["conv_stem.weight"] = (stem, 3, 3, 3)
+    bn("bn1", stem)
+    for b in blocks:
+        p = b["key"]
+        if b["type"] == "ds":
+            s[p + ".conv_dw.weight"] = (b["cin"], 1, b["k"], b["k"])
+            bn(p + ".bn1", b["cin"])
+            if b["se"]:
+                se(p, b["cin"], b["se"])
+            s[p + ".conv_pw.weight"] = (b["cout"], b["cin"], 1, 1)
+            bn(p + ".bn2", b["cout"])
+        elif b["type"] == "ir":
+            s[p + ".conv_pw.weight"] = (b["mid"], b["cin"], 1, 1)
+            bn(p + ".bn1", b["mid"])
+            s[p + ".conv_dw.weight"] = (b["mid"], 1, b["k"], b["k"])
+            bn(p + ".bn2", b["mid"])
+            if b["se"]:
+                se(p, b["mid"], b["se"])
+            s[p + ".conv_pwl.weight"] = (b["cout"], b["mid"], 1, 1)
+            bn(p + ".bn3", b["cout"])
+        else:
+            s[p + ".conv.weight"] = (b["cout"], b["cin"], 1, 1)
+            bn(p + ".bn1", b["cout"])
+    s["conv_head.weight"] = (nf, blocks[-1]["cout"], 1, 1)
+    s["conv_head.bias"] = (nf,)
+    if num_classes:
+        s["classifier.weight"] = (num_classes, nf)
+        s["classifier.bias"] = (num_classes,)
+    return s
+
+
+def mobilenetv3_num_learnable(arch, num_classes=0):
+    """Learnable parameters (BN running statistics excluded) of the builder's table, with an optional classifier."""
+    n = 0
+    for k, shp in _mobilenetv3_shapes(arch, num_classes).items():
+        if not k.endswith(("running_mean", "running_var")):
+            n += math.prod(shp)
+    return n
 
 
 def init_state_dict(arch, seed=0, img_size=224, scale="unit"):
@@ -140,10 +267,12 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit"):
     LN/BN affine terms and running statistics, so that attention is far from uniform and every
     term of every kernel (biases, gamma/beta, BN folding) is exercised by the parity tests.
     The generator is the CPU Philox stream, identical on every machine with this torch build.
-    ConvNeXt (_init_convnext) draws from the same generator with rules of its own.
+    ConvNeXt (_init_convnext) and MobileNetV3 (_init_mobilenetv3) draw from generators of their own with rules of their own.
     """
     if arch in CONVNEXT_CFG:
         return _init_convnext(arch, seed, img_size, scale)
+    if arch in MOBILENETV3_CFG:
+        return _init_mobilenetv3(arch, seed, img_size, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -233,6 +362,41 @@ def _init_convnext(arch, seed, img_size, scale):
     return sd
 
 
+def _init_mobilenetv3(arch, seed, img_size, scale):
+    """MobileNetV3 seeded init.  scale="timm": timm's _init_weight_goog (convs N(0, sqrt(2 / fan_out)) with fan_out = k*k*out / groups,
+    zero biases, BN at identity with running statistics 0 / 1).  scale="unit": fan-in-scaled convs, BN gains U(0.5, 1.5), shifts and
+    running means N(0, 0.1), running variances U(0.5, 2.0), conv biases N(0, 0.1): every term of the BN folding is exercised."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    sd = OrderedDict()
+
+    def randn(shape, std):
+        return torch.randn(shape, generator=g, dtype=torch.float32) * std
+
+    def uniform(shape, lo, hi):
+        return torch.rand(shape, generator=g, dtype=torch.float32) * (hi - lo) + lo
+
+    for k, shp in param_shapes(arch, img_size).items():
+        leaf = k.rsplit(".", 1)[-1]
+        if len(shp) == 4:
+            dw = shp[1] == 1 and shp[2] > 1
+            if scale == "timm":
+                fan_out = shp[2] * shp[3] * (1 if dw else shp[0])
+                v = randn(shp, math.sqrt(2.0 / fan_out))
+            else:
+                v = randn(shp, 1.0 / math.sqrt(shp[1] * shp[2] * shp[3]))
+        elif scale == "timm":
+            v = torch.ones(shp) if leaf in ("weight", "running_var") else torch.zeros(shp)
+        elif leaf == "weight":
+            v = uniform(shp, 0.5, 1.5)
+        elif leaf == "running_var":
+            v = uniform(shp, 0.5, 2.0)
+        else:
+            v = randn(shp, 0.1)
+        sd[k] = v.contiguous()
+    return sd
+
+
 def strip_prefix(sd, prefix="net."):
     """models/encoders.py:60 keeps the timm module as ``self.net`` -> keys ``net.<timm key>``."""
     keys = list(sd.keys())
@@ -284,6 +448,11 @@ def infer_arch(sd):
                        for i in range(4))
         for name, (dep, wid) in CONVNEXT_CFG.items():
             if dep == depths and wid == widths:
+                return name
+    if "conv_stem.weight" in sd and "conv_head.weight" in sd:
+        for name in MOBILENETV3_CFG:
+            want = param_shapes(name)
+            if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
                 return name
     raise ValueError("cannot infer encoder architecture from checkpoint keys")
 

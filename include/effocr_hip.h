@@ -61,10 +61,13 @@ const char* effocr_last_error(void);
  * ------------------------------------------------------------------------------------------ */
 typedef struct effocr_encoder effocr_encoder_t;
 
-/* arch: "resnet18" | "vit_small_patch16_224" | "vit_base_patch16_224" | "convnext_tiny" ("vit_tiny_test" for tests).
- * img_size: input H = W (224 for the ViTs' pos_embed; any positive multiple of 32 for resnet18 and convnext_tiny).
- * convnext_tiny (timm convnext.py key names, embed_dim 768) runs in all three precisions; its embeddings are bitwise independent of
- * the call size and of effocr_encoder_set_chunk. */
+/* arch: "resnet18" | "vit_small_patch16_224" | "vit_base_patch16_224" | "convnext_tiny" | "mobilenetv3_small_050"
+ * ("vit_tiny_test" for tests).
+ * img_size: input H = W (224 for the ViTs' pos_embed; any positive multiple of 32 for resnet18 and convnext_tiny; a multiple of 32
+ * from 32 to 224 for mobilenetv3_small_050, anything else is EFFOCR_EINVAL).
+ * convnext_tiny (timm convnext.py key names, embed_dim 768) and mobilenetv3_small_050 (timm mobilenetv3.py key names, embed_dim 1024,
+ * the output of conv_head + hard-swish) run in all three precisions and take fp32 crops only; their embeddings are bitwise
+ * independent of the call size and of effocr_encoder_set_chunk. */
 int effocr_encoder_create(const char* arch, int img_size, int precision, effocr_encoder_t** out);
 void effocr_encoder_destroy(effocr_encoder_t* enc);
 int effocr_encoder_embed_dim(const effocr_encoder_t* enc);
@@ -102,7 +105,7 @@ int effocr_encoder_forward_ex(effocr_encoder_t* enc, const void* x_dev, int x_dt
  * tools/ubench/mfma_f16_vs_bf16.hip measures 2.37 GHz idle-data, 1.73 GHz (bf16) / 1.58 GHz (f16) under saturated MFMA load. */
 int effocr_clock_sample(void* out_dev, void* stream);
 
-/* Status of EVERY forward issued with this workspace since the previous check (ViT and ConvNeXt; resnet18 is fp32 throughout and always
+/* Status of EVERY forward issued with this workspace since the previous check (ViT, ConvNeXt and MobileNetV3; resnet18 is fp32 throughout and always
  * reports OK): the forward keeps an int32 status word at workspace offset 0 and only ever ORs into it (its last kernel); this call
  * copies it on `stream`, synchronises the stream, CLEARS it if it was set and returns EFFOCR_EOVERFLOW if an embedding came out
  * non-finite — one check covers the slices of a large call, internal sub-batches and any number of asynchronous forwards (ABI 6;
@@ -116,8 +119,8 @@ int effocr_encoder_check_status(const effocr_encoder_t* enc, const void* workspa
 /* zero the status word of a (freshly allocated) workspace, asynchronously on `stream` */
 int effocr_encoder_reset_status(const effocr_encoder_t* enc, void* workspace_dev, void* stream);
 
-/* ViT and ConvNeXt: run the forward in internal sub-batches of `crops_per_chunk` crops (ViT: 0 = whole batch; ConvNeXt: 0 = as many
- * crops as keep the workspace under 1 GB, at most 192) so that the activations between consecutive kernels stay in the 256 MiB
+/* ViT, ConvNeXt and MobileNetV3: run the forward in internal sub-batches of `crops_per_chunk` crops (ViT: 0 = whole batch; ConvNeXt:
+ * 0 = as many crops as keep the workspace under 1 GB, at most 192; MobileNetV3: 0 = as many as keep it under 128 MiB, at most 512) so that the activations between consecutive kernels stay in the 256 MiB
  * Infinity Cache.  Results are identical for every setting; it only changes the workspace size and the launch count. */
 int effocr_encoder_set_chunk(effocr_encoder_t* enc, int crops_per_chunk);
 /* tuning / A-B switches (ViT, 16-bit precisions; every combination is parity-tested against the oracle,
