@@ -173,6 +173,49 @@ def lib():
     return _lib
 
 
+# libeffocr_head.so (include/effocr_head.h): the FFNN classifier head, a library of its own because libeffocr_hip.so is at its size cap.
+# Bound by head_lib(); its functions are not part of EXPORTS (the product library's ABI, checked against effocr_hip.h).
+HEAD_SO_PATH = os.path.join(_HERE, "libeffocr_head.so")
+HEAD_ABI_VERSION = 1     # == EFFOCR_HEAD_ABI_VERSION of include/effocr_head.h
+HEAD_EXPORTS = ("effocr_head_abi_version", "effocr_head_last_error", "effocr_classifier_head_workspace_bytes",
+                "effocr_classifier_head")
+_head = None
+
+
+def head_lib():
+    """Load (once) and return the ctypes handle of libeffocr_head.so; raises if it is missing or its ABI version differs."""
+    global _head
+    with _lock:
+        if _head is None:
+            if not os.path.exists(HEAD_SO_PATH):
+                raise EffOCRHipError(f"{HEAD_SO_PATH} not found: the classifier head library is required (no CPU fallback). "
+                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
+            c = ctypes
+            handle = c.CDLL(HEAD_SO_PATH)
+            sig = {
+                "effocr_head_abi_version": (c.c_int, []),
+                "effocr_head_last_error": (c.c_char_p, []),
+                "effocr_classifier_head_workspace_bytes": (c.c_size_t, [c.c_int64, c.c_int]),
+                "effocr_classifier_head": (c.c_int, [c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]),
+            }
+            for name in HEAD_EXPORTS:
+                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
+                fn.restype, fn.argtypes = sig[name]
+            got = handle.effocr_head_abi_version()
+            if got != HEAD_ABI_VERSION:
+                raise EffOCRHipError(f"libeffocr_head.so ABI version {got} != {HEAD_ABI_VERSION} expected by this package: rebuild "
+                                     "(make -C effocr_amd/csrc)")
+            _head = handle
+    return _head
+
+
+def head_check(rc, what=""):
+    if rc != 0:
+        msg = head_lib().effocr_head_last_error()
+        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
 def check(rc, what="", handle=None):
     """``handle``: the library the failing call was made through (engines pass the one they were created with — last_error is
     per shared object, and use_library() may have switched the process default since)."""

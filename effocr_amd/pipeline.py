@@ -148,6 +148,45 @@ class Recognizer:
         return self(crops)
 
 
+def read_class_map(path):
+    """``class_map.json`` of the FFNN mode -> {str(class id): glyph}, read as infer_effocr.py:219-220 reads it (json.load)."""
+    import json
+    with open(path) as f:
+        return json.load(f)
+
+
+class ClassifierRecognizer:
+    """The FFNN branch of ``EffOCR.infer`` (infer_effocr.py:325-333, 337-338) as one object: crops -> encoder -> classifier head ->
+    fused argmax -> ``class_map_dict[str(id)]``, with ``Recognizer.__call__``'s contract, so ``postprocess.LineRecognizer`` and
+    ``recognize_boxes`` take it unchanged.  ``classifier`` is an ``effocr_amd.classifiers.AutoClassifierFactory(...)`` instance (or
+    anything with ``predict(x) -> ids``).  The reference's quirks stay: a class mapped to " " is "" in ``output_nns`` (``.strip()``),
+    the line string is stripped, and an id missing from the map raises KeyError."""
+
+    def __init__(self, classifier, class_map_dict):
+        self.recongizer_encoder = classifier       # sic — attribute name of infer_effocr.py:224 (LineRecognizer reads its img_size)
+        self.recognizer = classifier               # infer_effocr.py:222: in the FFNN mode the recognizer IS the classifier
+        self.class_map_dict = class_map_dict
+
+    def predict(self, crops):
+        """crops: [B,3,H,W] float32 tensor (or list of [3,H,W]) -> int64 ids [B] on the classifier's device."""
+        if isinstance(crops, (list, tuple)):
+            crops = torch.stack(list(crops))
+        dev = encoder_device(self.recongizer_encoder)
+        if dev is not None:
+            crops = crops.to(dev)
+        return self.recognizer.predict(crops)
+
+    def __call__(self, crops):
+        predlist = self.predict(crops).cpu().tolist()                # (.cpu(): the call's synchronisation point)
+        check_encoder_status(self.recongizer_encoder)
+        nearest_chars = [[self.class_map_dict[str(x)]] for x in predlist]
+        output_nns = ["".join(chars).strip() for chars in nearest_chars]
+        output = "".join(x[0] for x in nearest_chars).strip()
+        return nearest_chars, output_nns, output
+
+    recognize_boxes = Recognizer.recognize_boxes
+
+
 class RecognizerEngineExecutorThread(threading.Thread):
     """infer_effocr_onnx_multi.py:207-223: pulls ``(i, batch)`` pairs off a queue until it is empty, runs ``iteration``
     on the SHARED engine and posts ``(i, output)``.  (``get_nowait`` instead of the reference's ``empty()`` + blocking

@@ -120,8 +120,50 @@ def is_convnext(arch):
     return arch in CONVNEXT_CFG
 
 
-def param_shapes(arch, img_size=224):
-    """Ordered {timm key: shape} for ``arch`` (buffers such as BN running stats included)."""
+# timm's classifier head per family: (weight key, bias key) of the nn.Linear that ``timm.create_model(name, num_classes=N)`` appends
+# (models/classifiers.py:35-83).  Its input is the encoder's embedding before L2 normalisation (HipEncoder.forward(x, normalize=False)):
+# resnet18 the global-pooled features, ViT norm(x)[:, 0] (fc_norm is Identity for token pooling), convnext_tiny the output of head.norm,
+# mobilenetv3 conv_head + hard-swish.
+HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bias"),
+             "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias")}
+
+
+def _family(arch):
+    if arch in VIT_CFG:
+        return "vit"
+    if arch in RESNET_CFG:
+        return "resnet"
+    if arch in CONVNEXT_CFG:
+        return "convnext"
+    if arch in MOBILENETV3_CFG:
+        return "mobilenetv3"
+    raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def head_keys(arch):
+    """(weight key, bias key) of ``arch``'s timm classifier head."""
+    return HEAD_KEYS[_family(arch)]
+
+
+def head_shapes(arch, num_classes):
+    """Ordered {timm key: shape} of the classifier head: weight [num_classes, embed_dim], bias [num_classes] (empty for 0)."""
+    s = OrderedDict()
+    if num_classes:
+        if num_classes < 0:
+            raise ValueError(f"num_classes must be >= 0, got {num_classes}")
+        wk, bk = head_keys(arch)
+        s[wk] = (int(num_classes), embed_dim(arch))
+        s[bk] = (int(num_classes),)
+    return s
+
+
+def param_shapes(arch, img_size=224, num_classes=0):
+    """Ordered {timm key: shape} for ``arch`` (buffers such as BN running stats included); with ``num_classes`` > 0 timm's classifier
+    head comes last, as in timm's state dict."""
+    if num_classes:
+        s = param_shapes(arch, img_size)
+        s.update(head_shapes(arch, num_classes))
+        return s
     s = OrderedDict()
     if arch in VIT_CFG:
         D, depth, heads, r = VIT_CFG[arch]
@@ -259,7 +301,7 @@ def mobilenetv3_num_learnable(arch, num_classes=0):
     return n
 
 
-def init_state_dict(arch, seed=0, img_size=224, scale="unit"):
+def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
     """Seeded random-init fp32 CPU state dict with timm key names.
 
     scale="timm": trunc_normal(0.02) linears / kaiming convs, LN and BN at identity — what
@@ -268,7 +310,13 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit"):
     term of every kernel (biases, gamma/beta, BN folding) is exercised by the parity tests.
     The generator is the CPU Philox stream, identical on every machine with this torch build.
     ConvNeXt (_init_convnext) and MobileNetV3 (_init_mobilenetv3) draw from generators of their own with rules of their own.
+    ``num_classes`` > 0 appends timm's classifier head, drawn from a generator of its own (init_head): the encoder's
+    parameters are the same with and without a head.
     """
+    if num_classes:
+        sd = init_state_dict(arch, seed, img_size, scale)
+        sd.update(init_head(arch, num_classes, seed, scale))
+        return sd
     if arch in CONVNEXT_CFG:
         return _init_convnext(arch, seed, img_size, scale)
     if arch in MOBILENETV3_CFG:
@@ -397,6 +445,32 @@ def _init_mobilenetv3(arch, seed, img_size, scale):
     return sd
 
 
+def init_head(arch, num_classes, seed=0, scale="unit"):
+    """Seeded classifier head from a CPU Philox generator of its own (seeded from ``seed`` and the tag 0x68656164): scale="unit"
+    gives weights N(0, 1/D) and biases N(0, 0.1), so logits are O(1) for O(1) embeddings; scale="timm" gives timm's
+    trunc_normal(0.02) weight and zero bias."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x68656164) % (1 << 63))
+    out = OrderedDict()
+    (wk, wshape), (bk, bshape) = head_shapes(arch, num_classes).items()
+    if scale == "timm":
+        out[wk] = (torch.randn(wshape, generator=g, dtype=torch.float32) * 0.02).clamp_(-0.04, 0.04).contiguous()
+        out[bk] = torch.zeros(bshape)
+    else:
+        out[wk] = (torch.randn(wshape, generator=g, dtype=torch.float32) / math.sqrt(wshape[1])).contiguous()
+        out[bk] = (torch.randn(bshape, generator=g, dtype=torch.float32) * 0.1).contiguous()
+    return out
+
+
+def infer_num_classes(sd):
+    """Classes of the timm classifier head a checkpoint carries (rows of its head weight), 0 when it has none."""
+    sd = strip_prefix(sd)
+    for wk, bk in HEAD_KEYS.values():
+        if wk in sd and bk in sd and sd[wk].dim() == 2:
+            return int(sd[wk].shape[0])
+    return 0
+
+
 def strip_prefix(sd, prefix="net."):
     """models/encoders.py:60 keeps the timm module as ``self.net`` -> keys ``net.<timm key>``."""
     keys = list(sd.keys())
@@ -457,9 +531,10 @@ def infer_arch(sd):
     raise ValueError("cannot infer encoder architecture from checkpoint keys")
 
 
-def check_state_dict(arch, sd, img_size=224):
-    """Raise ValueError listing missing / mis-shaped parameters (num_batches_tracked etc. ignored)."""
-    want = param_shapes(arch, img_size)
+def check_state_dict(arch, sd, img_size=224, num_classes=0):
+    """Raise ValueError listing missing / mis-shaped parameters (num_batches_tracked etc. ignored); with ``num_classes`` > 0 the
+    classifier head is required too."""
+    want = param_shapes(arch, img_size, num_classes)
     bad = []
     for k, shp in want.items():
         if k not in sd:
