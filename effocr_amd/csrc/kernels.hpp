@@ -201,6 +201,10 @@ int im2col_nchw(const float* x, float* col, int B, int Cin, int H, int W, int KH
 // wt (optional): the same weights transposed to [108 taps][32 channels] — with it, an even W and an 8-byte aligned x the scalar-weight kernel runs
 int stem6x6s2_nchw(const float* x, const float* w, int w_ld, const float* wt, const float* bias, float* out, int B, int H, int W, int OH, int OW, int out_ld,
                    int out_off, int silu, hipStream_t s);
+// the same stem (+ SiLU) for the other YOLOv5 widths (n / m / l / x): wt [108 taps][wt_ld], channels in groups of 16, OW % 4 == 0;
+// out channels out_off .. +cout_st (a multiple of 16; weight rows and bias zero from cout on: the channel padding to 32 of n / m / x)
+int stem6x6s2_g16_nchw(const float* x, const float* wt, int wt_ld, const float* bias, float* out, int B, int H, int W, int OH, int OW, int out_ld,
+                       int out_off, int cout, int cout_st, hipStream_t s);
 int upsample2x_nhwc(const float* in, int in_ld, int in_off, float* out, int out_ld, int out_off, int B, int H, int W, int C, hipStream_t s);
 int maxpool5_nhwc(const float* in, int in_ld, int in_off, float* out, int out_ld, int out_off, int B, int H, int W, int C, hipStream_t s);
 // Detect head decode of one level: raw [B,ny,nx,raw_ld] (channel a*no + o) -> pred [B,total,no] rows row0 + (a*ny + y)*nx + x

@@ -4,6 +4,7 @@
 // the network's concatenations (C3, SPPF, neck) are never copied.  The convolutions themselves are resnet.hip's
 // implicit-GEMM kernel (exact fp32 MFMA) with a SiLU epilogue.
 //   im2col_nchw     stem conv (3 input channels, 6x6 / stride 2): rows for the 1x1 implicit GEMM
+//   stem6x6s2_*     the same stem straight from NCHW: 32 channels (yolov5s), or groups of 16 for the other widths
 //   upsample2x      nn.Upsample(scale_factor=2, mode="nearest")
 //   maxpool5        nn.MaxPool2d(5, 1, 2) (SPPF)
 //   yolo_decode     ultralytics Detect.forward in inference mode: sigmoid, grid / anchor decode, (bs, na*ny*nx, no) layout
@@ -175,6 +176,66 @@ __global__ __launch_bounds__(256, 2) void stem6x6s2_sw_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) r[e] = silu_fast(r[e]);
       }
+      *reinterpret_cast<f32x4*>(o + 4 * q) = r;
+    }
+  }
+}
+
+// The stem at the other widths (yolov5n / m / l / x: 16 / 48 / 64 / 80 channels, stored with a channel stride padded to 32, 64, 64, 96):
+// the scalar-weight scheme above over channel GROUPS of 16 (blockIdx.y) instead of one kernel instance per width.  A thread owns four
+// horizontally adjacent pixels (OW % 4 == 0) x 16 channels (64 accumulators) and walks the 18 (ky, c) input rows, 6 taps each; the
+// weights come from the [tap][wt_ld] transpose at a uniform address, so through the scalar cache.  Inputs as single floats, clamped
+// and selected (no alignment or parity demand on x or W).  A group at or above `cout` is the zero padding the next layer's implicit
+// GEMM reads: it skips the taps, and its zero bias gives SiLU(0) = 0.  SiLU always (the stem is a Conv block).
+__global__ __launch_bounds__(256) void stem6x6s2_g16_kernel(const float* __restrict__ x, const float* __restrict__ wt, int wt_ld, const float* __restrict__ bias,
+                                                            float* __restrict__ out, int B, int H, int W, int OH, int OW, int out_ld, int out_off, int cout) {
+  const int OW4 = OW >> 2;
+  const int id = (int)blockIdx.x * 256 + (int)threadIdx.x;           // B * OH * OW / 4 < 2^31 (checked by the launcher)
+  if (id >= B * OH * OW4) return;
+  const int g0 = blockIdx.y * 16;
+  const int ox = id % OW4 * 4, oy = id / OW4 % OH, b = id / (OW4 * OH);
+  float acc[4][16];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int co = 0; co < 16; ++co) acc[p][co] = 0.f;
+  if (g0 < cout) {
+    const int ix0 = ox * 2 - 2;
+#pragma unroll 1
+    for (int r = 0; r < 18; ++r) {                           // (ky, c): one input row of 12 columns, its 6 taps unrolled
+      const int ky = r / 3, c = r - 3 * ky, iy = oy * 2 - 2 + ky;
+      const bool rowok = iy >= 0 && iy < H;
+      const float* xr = x + ((int64_t)(b * 3 + c) * H + min(max(iy, 0), H - 1)) * W;
+      float v[12];
+#pragma unroll
+      for (int j = 0; j < 12; ++j) {                         // the zero padding as a bit mask on a clamped (always valid) load
+        const int ix = ix0 + j;
+        const unsigned keep = (rowok && ix >= 0 && ix < W) ? ~0u : 0u;
+        v[j] = __uint_as_float(__float_as_uint(xr[min(max(ix, 0), W - 1)]) & keep);
+      }
+#pragma unroll
+      for (int kx = 0; kx < 6; ++kx) {
+        const float* wr = wt + (size_t)((ky * 6 + kx) * 3 + c) * wt_ld + g0;     // uniform address: scalar loads
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + 4 * q);
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[p][4 * q + e] = fmaf(v[kx + 2 * p], wv[e], acc[p][4 * q + e]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    float* o = out + ((int64_t)(b * OH + oy) * OW + ox + p) * out_ld + out_off + g0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + g0 + 4 * q);
+      f32x4 r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = silu_fast(acc[p][4 * q + e] + bv[e]);
       *reinterpret_cast<f32x4*>(o + 4 * q) = r;
     }
   }
@@ -573,6 +634,18 @@ int stem6x6s2_nchw(const float* x, const float* w, int w_ld, const float* wt, co
   }
   hipLaunchKernelGGL(stem6x6s2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, w_ld, bias, out, B, H, W, OH, OW, out_ld, out_off, silu);
   return check_launch("stem6x6s2");
+}
+
+int stem6x6s2_g16_nchw(const float* x, const float* wt, int wt_ld, const float* bias, float* out, int B, int H, int W, int OH, int OW, int out_ld,
+                       int out_off, int cout, int cout_st, hipStream_t s) {
+  const int64_t total = (int64_t)B * OH * (OW / 4);
+  if (total <= 0) return EFFOCR_OK;
+  if (total >= ((int64_t)1 << 31) - 256) return fail(EFFOCR_EUNSUPPORTED, "stem conv (16-channel groups): too many output pixels");
+  if (OW % 4 || cout_st % 16 || cout < 1 || cout > cout_st || wt_ld < cout_st || (wt_ld & 3) || ((out_ld | out_off) & 3) || out_off + cout_st > out_ld)
+    return fail(EFFOCR_EINVAL, "stem conv (16-channel groups): OW and strides multiples of 4, stored channels a multiple of 16 inside the output row");
+  hipLaunchKernelGGL(stem6x6s2_g16_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)(cout_st / 16)), dim3(256), 0, s, x, wt, wt_ld, bias, out, B, H, W,
+                     OH, OW, out_ld, out_off, cout);
+  return check_launch("stem6x6s2_g16");
 }
 
 int upsample2x_nhwc(const float* in, int in_ld, int in_off, float* out, int out_ld, int out_off, int B, int H, int W, int C, hipStream_t s) {

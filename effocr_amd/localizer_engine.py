@@ -6,8 +6,9 @@ image to ``input_shape`` (:75-85,107-138), runs the network, and ``_postprocess`
 tensors ``(x1, y1, x2, y2, conf, cls)`` in letterboxed-input pixels.  The driver reads ``result[:, :4]`` and ``result[:, -1]``
 (infer_effocr_onnx_multi.py:252-256: class 0 = characters, class 1 = words).
 
-Here ``model_path`` is a torch state dict (``.pt`` / ``.pth`` / ``.safetensors``, or a dict) with the ultralytics YOLOv5s keys
-(``model.0.conv.weight`` ... ``model.24.m.2.bias``, ``model.24.anchors``) instead of an ``.onnx`` graph; everything from the
+Here ``model_path`` is a torch state dict (``.pt`` / ``.pth`` / ``.safetensors``, or a dict) with the ultralytics YOLOv5 keys
+(``model.0.conv.weight`` ... ``model.24.m.2.bias``, ``model.24.anchors``) of any v6 scale — n, s, m, l or x, read from the
+checkpoint by ``yolov5_scale`` — instead of an ``.onnx`` graph; everything from the
 uint8 image to the kept boxes runs on the device (letterbox kernel -> fp32-MFMA convolutions -> decode -> NMS kernels):
 one uint8 upload and one tiny ``[n,6]`` download per image.  Only the ``yolo`` backend exists (the detectron2 / mmdetection
 branches of the reference return raw session outputs and are out of scope).
@@ -51,8 +52,21 @@ def letterbox_geometry(shape, new_shape=(640, 640), auto=False, scaleFill=False,
     return new_unpad[1], new_unpad[0], top, bottom, left, right, ratio, (dw, dh)
 
 
-def yolov5s_param_shapes(nc):
-    """{ultralytics key: shape} of YOLOv5s (v6 yaml, width 0.5 / depth 0.33) with ``nc`` classes."""
+# ultralytics YOLOv5 v6 scales: models/yolov5{n,s,m,l,x}.yaml are one layer table at these (depth_multiple, width_multiple)
+YOLOV5_SCALES = {"n": (0.33, 0.25), "s": (0.33, 0.50), "m": (0.67, 0.75), "l": (1.00, 1.00), "x": (1.33, 1.25)}
+
+
+def _yolov5_dims(scale):
+    """(channels(c), repeats(n)) of parse_model at ``scale``: make_divisible(c * width, 8) and max(round(n * depth), 1)."""
+    if scale not in YOLOV5_SCALES:
+        raise ValueError(f"unknown YOLOv5 scale {scale!r} (one of {', '.join(YOLOV5_SCALES)})")
+    depth, width = YOLOV5_SCALES[scale]
+    return (lambda c: math.ceil(c * width / 8) * 8), (lambda n: max(round(n * depth), 1) if n > 1 else n)
+
+
+def yolov5_param_shapes(nc, scale="s"):
+    """{ultralytics key: shape} of YOLOv5<scale> (v6 yaml, ``scale`` in "nsmlx") with ``nc`` classes, in module order."""
+    ch, rep = _yolov5_dims(scale)
     shapes = {}
 
     def conv(name, c1, c2, k):
@@ -65,42 +79,48 @@ def yolov5s_param_shapes(nc):
         conv(name + ".cv1", c1, c_, 1)
         conv(name + ".cv2", c1, c_, 1)
         conv(name + ".cv3", 2 * c_, c2, 1)
-        for i in range(n):
+        for i in range(rep(n)):
             conv(f"{name}.m.{i}.cv1", c_, c_, 1)
             conv(f"{name}.m.{i}.cv2", c_, c_, 3)
 
-    conv("model.0", 3, 32, 6)
-    conv("model.1", 32, 64, 3)
-    c3("model.2", 64, 64, 1)
-    conv("model.3", 64, 128, 3)
-    c3("model.4", 128, 128, 2)
-    conv("model.5", 128, 256, 3)
-    c3("model.6", 256, 256, 3)
-    conv("model.7", 256, 512, 3)
-    c3("model.8", 512, 512, 1)
-    conv("model.9.cv1", 512, 256, 1)
-    conv("model.9.cv2", 1024, 512, 1)
-    conv("model.10", 512, 256, 1)
-    c3("model.13", 512, 256, 1)
-    conv("model.14", 256, 128, 1)
-    c3("model.17", 256, 128, 1)
-    conv("model.18", 128, 128, 3)
-    c3("model.20", 256, 256, 1)
-    conv("model.21", 256, 256, 3)
-    c3("model.23", 512, 512, 1)
-    for l, c in enumerate((128, 256, 512)):
+    c64, c128, c256, c512, c1024 = ch(64), ch(128), ch(256), ch(512), ch(1024)
+    conv("model.0", 3, c64, 6)
+    conv("model.1", c64, c128, 3)
+    c3("model.2", c128, c128, 3)
+    conv("model.3", c128, c256, 3)
+    c3("model.4", c256, c256, 6)
+    conv("model.5", c256, c512, 3)
+    c3("model.6", c512, c512, 9)
+    conv("model.7", c512, c1024, 3)
+    c3("model.8", c1024, c1024, 3)
+    conv("model.9.cv1", c1024, c1024 // 2, 1)
+    conv("model.9.cv2", c1024 // 2 * 4, c1024, 1)
+    conv("model.10", c1024, c512, 1)
+    c3("model.13", 2 * c512, c512, 3)
+    conv("model.14", c512, c256, 1)
+    c3("model.17", 2 * c256, c256, 3)
+    conv("model.18", c256, c256, 3)
+    c3("model.20", 2 * c256, c512, 3)
+    conv("model.21", c512, c512, 3)
+    c3("model.23", 2 * c512, c1024, 3)
+    for l, c in enumerate((c256, c512, c1024)):
         shapes[f"model.24.m.{l}.weight"] = (3 * (nc + 5), c, 1, 1)
         shapes[f"model.24.m.{l}.bias"] = (3 * (nc + 5),)
     shapes["model.24.anchors"] = (3, 3, 2)
     return shapes
 
 
-def init_yolov5s_state_dict(nc=2, seed=0):
-    """Seeded random YOLOv5s weights (there is no network to fetch a trained localizer): kaiming-uniform convolutions,
+def yolov5s_param_shapes(nc):
+    """{ultralytics key: shape} of YOLOv5s (v6 yaml, width 0.5 / depth 0.33) with ``nc`` classes."""
+    return yolov5_param_shapes(nc, "s")
+
+
+def init_yolov5_state_dict(nc=2, scale="s", seed=0):
+    """Seeded random YOLOv5<scale> weights (there is no network to fetch a trained localizer): kaiming-uniform convolutions,
     BatchNorm with non-trivial statistics, ultralytics' Detect bias initialisation, the default COCO anchors."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for k, shp in yolov5s_param_shapes(nc).items():
+    for k, shp in yolov5_param_shapes(nc, scale).items():
         if k.endswith("conv.weight") or (k.startswith("model.24.m.") and k.endswith(".weight")):
             fan_in = shp[1] * shp[2] * shp[3]
             bound = math.sqrt(3.0 / fan_in) * 1.2
@@ -122,6 +142,44 @@ def init_yolov5s_state_dict(nc=2, seed=0):
     return sd
 
 
+def init_yolov5s_state_dict(nc=2, seed=0):
+    """Seeded random YOLOv5s weights (``init_yolov5_state_dict(nc, "s", seed)``)."""
+    return init_yolov5_state_dict(nc, "s", seed)
+
+
+def _shape_mismatches(state_dict, want):
+    bad = [f"missing {k}" for k in want if k not in state_dict] + \
+          [f"{k}: shape {tuple(state_dict[k].shape)} != {tuple(want[k])}" for k in want if k in state_dict and tuple(state_dict[k].shape) != tuple(want[k])]
+    return bad
+
+
+def yolov5_scale(state_dict):
+    """The v6 scale ("n" | "s" | "m" | "l" | "x") of an ultralytics YOLOv5 detection state dict: width from the stem's output channels
+    (``model.0.conv.weight``), depth from the number of bottlenecks in ``model.2.m``; every other key and shape must then match that
+    scale's table.  ValueError names the mismatch."""
+    key = "model.24.m.0.bias"
+    if key not in state_dict:
+        raise ValueError(f"state dict has no '{key}': not an ultralytics YOLOv5 detection model")
+    if "model.0.conv.weight" not in state_dict:
+        raise ValueError("state dict has no 'model.0.conv.weight': not an ultralytics YOLOv5 detection model")
+    nc = int(state_dict[key].numel()) // 3 - 5
+    c0 = int(state_dict["model.0.conv.weight"].shape[0])
+    nm = len({k.split(".")[3] for k in state_dict if k.startswith("model.2.m.")})
+    by_width = [s for s in YOLOV5_SCALES if _yolov5_dims(s)[0](64) == c0]
+    if not by_width:
+        raise ValueError(f"model.0.conv.weight has {c0} output channels: no YOLOv5 v6 scale has that width "
+                         f"({', '.join(f'{s}: {_yolov5_dims(s)[0](64)}' for s in YOLOV5_SCALES)})")
+    by_depth = [s for s in by_width if _yolov5_dims(s)[1](3) == nm]
+    if not by_depth:
+        raise ValueError(f"model.2.m has {nm} bottlenecks, but a stem of {c0} channels is YOLOv5{by_width[0]} with "
+                         f"{_yolov5_dims(by_width[0])[1](3)}")
+    scale = by_depth[0]
+    bad = _shape_mismatches(state_dict, yolov5_param_shapes(nc, scale))
+    if bad:
+        raise ValueError(f"state dict does not match yolov5{scale}: " + "; ".join(bad[:6]) + (f" (+{len(bad) - 6} more)" if len(bad) > 6 else ""))
+    return scale
+
+
 def _load_state_dict(model_path):
     if isinstance(model_path, dict):
         sd = model_path
@@ -136,9 +194,10 @@ def _load_state_dict(model_path):
 
 
 class HipLocalizer:
-    """Device-resident YOLOv5s: C-ABI handle + weight blob + per-stream workspaces."""
+    """Device-resident YOLOv5 (any v6 scale n / s / m / l / x): C-ABI handle + weight blob + per-stream workspaces."""
 
-    def __init__(self, state_dict, input_shape=(640, 640), device=None, precision="fp32"):
+    def __init__(self, state_dict, input_shape=(640, 640), device=None, precision="fp32", arch=None):
+        # arch (optional): "yolov5n" ... "yolov5x"; must agree with the scale the state dict has (yolov5_scale)
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
         self.precision = precision
@@ -150,13 +209,12 @@ class HipLocalizer:
         no = int(state_dict[key].numel()) // 3
         self.nc, self.no = no - 5, no
         self.input_shape = (int(input_shape[0]), int(input_shape[1]))
-        want = yolov5s_param_shapes(self.nc)
-        bad = [f"missing {k}" for k in want if k not in state_dict] + \
-              [f"{k}: shape {tuple(state_dict[k].shape)} != {want[k]}" for k in want if k in state_dict and tuple(state_dict[k].shape) != tuple(want[k])]
-        if bad:
-            raise ValueError("state dict does not match yolov5s: " + "; ".join(bad[:6]) + (f" (+{len(bad) - 6} more)" if len(bad) > 6 else ""))
+        self.scale = yolov5_scale(state_dict)
+        self.arch = "yolov5" + self.scale
+        if arch is not None and arch != self.arch:
+            raise ValueError(f"arch={arch!r}, but the state dict is {self.arch}")
         self._h = ctypes.c_void_p()
-        _lib.check(self._L.effocr_localizer_create(b"yolov5s", self.nc, self.input_shape[0], self.input_shape[1], ctypes.byref(self._h)),
+        _lib.check(self._L.effocr_localizer_create(self.arch.encode(), self.nc, self.input_shape[0], self.input_shape[1], ctypes.byref(self._h)),
                    "effocr_localizer_create", self._L)
         for i in range(self._L.effocr_localizer_num_params(self._h)):
             name = self._L.effocr_localizer_param_name(self._h, i).decode()
@@ -281,9 +339,10 @@ class HipLocalizer:
 class EffLocalizer:
 
     def __init__(self, model_path, iou_thresh=0.01, conf_thresh=0.30, vertical=False, num_cores=None, providers=None,
-                 input_shape=(640, 640), model_backend='yolo', device=None, precision="fp32"):
+                 input_shape=(640, 640), model_backend='yolo', device=None, precision="fp32", arch=None):
         # precision (extension): "fp32" = fp32 MFMA operands (the oracle's arithmetic), "bf16" = bf16-rounded operands for every
         # convolution with an activation, fp32 accumulation and fp32 Detect heads (2-3x the network throughput)
+        # arch (extension): "yolov5n" ... "yolov5x" or None; the scale is read from the state dict and must agree (HipLocalizer)
         # num_cores / providers are ORT knobs (localizer_engine.py:17-23): accepted and ignored.
         if model_backend != 'yolo':
             raise NotImplementedError('Backend {} is not implemented'.format(model_backend))
@@ -291,7 +350,8 @@ class EffLocalizer:
         self._iou_thresh, self._conf_thresh, self._vertical = iou_thresh, conf_thresh, vertical
         self._input_shape = (int(input_shape[0]), int(input_shape[1]))
         self._model_backend = model_backend
-        self._eng_net = HipLocalizer(_load_state_dict(model_path), input_shape=self._input_shape, device=device, precision=precision)
+        self._eng_net = HipLocalizer(_load_state_dict(model_path), input_shape=self._input_shape, device=device, precision=precision,
+                                     arch=arch)
 
     def __call__(self, imgs):
         return self.run(imgs)

@@ -270,8 +270,10 @@ int effocr_crop_transform_batch_ex(const uint8_t* images_dev, int n_images, int6
  * Localizer engine: the YOLOv5 character / word detector the reference runs through ONNXRuntime
  * (onnx_engines/localizer_engine.py:14-66 EffLocalizer with model_backend == 'yolo'; driver
  * infer_effocr_onnx_multi.py:236-262).  Same handle protocol as the encoder: create -> set_param x N ->
- * upload -> forward.  arch "yolov5s" (ultralytics v6 yaml); parameter names are the ultralytics state-dict
- * keys ("model.0.conv.weight", "model.0.bn.running_var", ..., "model.24.m.2.bias", "model.24.anchors").
+ * upload -> forward.  arch "yolov5n" | "yolov5s" | "yolov5m" | "yolov5l" | "yolov5x": the ultralytics v6 yaml at depth / width
+ * 0.33 / 0.25, 0.33 / 0.50, 0.67 / 0.75, 1.00 / 1.00, 1.33 / 1.25 (anything else: EFFOCR_EUNSUPPORTED); parameter names are the
+ * ultralytics state-dict keys ("model.0.conv.weight", "model.0.bn.running_var", ..., "model.24.m.2.bias", "model.24.anchors"),
+ * listed by effocr_localizer_param_name in module order.  Weight and workspace sizes follow the scale.
  *   forward:  x_dev [B,3,in_h,in_w] fp32 (letterboxed RGB, 0..1 — what load_localizer_img builds, :75-85)
  *             -> pred_dev [B, num_predictions, 5 + num_classes] fp32 = the exported model's output 0
  *             (xywh in input pixels, objectness, class probabilities; 25200 rows at 640 x 640).
@@ -288,7 +290,7 @@ int effocr_localizer_upload(effocr_localizer_t* loc, void* weights_dev, size_t b
 /* "bf16_operands" [0]: 1 = every convolution that carries an activation runs with bf16-rounded operands (weights rounded once at
  * upload, activations in the stage loader) on v_mfma_f32_32x32x16_bf16, fp32 accumulation / bias / SiLU / residual; Detect's 1x1
  * heads keep fp32 operands.  0 = fp32 operands everywhere (v_mfma_f32_32x32x2_f32: the oracle's arithmetic up to summation order).
- * "direct_stem" [1]: the stem Conv(3, 32, 6, 2, 2) as a direct kernel from the NCHW input; 0 = im2col rows + the implicit GEMM (A/B
+ * "direct_stem" [1]: the stem Conv(3, c, 6, 2, 2) as a direct kernel from the NCHW input; 0 = im2col rows + the implicit GEMM (A/B
  * switch; set it before effocr_localizer_workspace_bytes — the im2col rows, 840 MB at 16 images, exist only on that path). */
 int effocr_localizer_set_option(effocr_localizer_t* loc, const char* name, int value);
 int64_t effocr_localizer_num_predictions(const effocr_localizer_t* loc);
