@@ -8,18 +8,24 @@ already resident in HBM, 10,000-row fp32 glyph index, k=10.  For N>1 (one proces
 torch.distributed.run, or by this script itself when WORLD_SIZE is not set) the default is BASELINE
 configs[2]: the SAME 1024 crops sharded over the ranks (``--scaling strong``: rank r encodes rows
 shard_bounds(1024, r, N), weights and index replicated) and one RCCL all_gather assembles the [1024, 10]
-ids on every rank; the weak-scaling figure (1024 crops per rank) is measured right after and reported
-under "weak".  ``--scaling weak`` makes the weak figure the headline instead.
+ids on every rank; with ``--full`` the weak-scaling figure (1024 crops per rank) is measured right after and
+reported under "weak".  ``--scaling weak`` makes the weak figure the headline instead.
 
 ``--dump-outputs DIR`` (rank 0) writes what the headline's last timed step returned — the top-k scores
 (knn_scores.npy, float32) and ids (knn_ids.npy, float64) of every crop — so that two builds can be
 compared output for output: the inputs are seeded, identical from run to run for the same arguments.
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, one fully profiled untimed step
+(it picks the kernel class that ``roofline`` times inside the timed region), the K timed steps, the dump and
+the line.  ``--full`` adds everything else the benchmark measures: the other scaling mode (N>1) and every
+object below but ``roofline`` (N=1; ``--no-extras`` / ``--no-cpu-baseline`` leave parts of it out again).
 
 Extra objects on the line:
   roofline      the dominant kernel class, timed live with HIP events recorded on the launch stream
                 INSIDE the timed region by the library's own profiler (effocr_encoder_profile_*):
                 achieved = algorithmic FLOPs per launch / mean launch duration, vs the dense bf16
                 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md).
+  --full only:
   cpu_baseline  rank 0, N=1 only: the CPU restatement of the reference path (oracle/: plain-torch
                 fp32 ViT-S + F.normalize + Q@X^T/top-k, i.e. PyTorch-CPU + IndexFlatIP semantics; timm
                 and faiss are tried first and their absence is recorded) on a bounded sample of the same workload.
@@ -87,8 +93,10 @@ def parse():
     ap.add_argument("--no-panel", action="store_true", help="A/B: K-streaming GEMM + standalone LayerNorm path")
     ap.add_argument("--scaling", default="auto", choices=["auto", "strong", "weak"],
                     help="N>1: strong = --batch crops in total, sharded (BASELINE configs[2]); weak = --batch crops per rank; auto = strong for N>1")
-    ap.add_argument("--no-extras", action="store_true", help="skip the small_batch and c4 objects (N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other scaling mode (N>1), the extra objects and the CPU baseline (N=1)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra objects (precision, small_batch, c1, c4, c5, ...; N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline object")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     ap.add_argument("--breakdown", action="store_true", help="also print a per-kernel-class table to stderr")
     ap.add_argument("--verify", action="store_true", help="N>1: check the all-gathered ids against rank 0 encoding every slice itself (exit 1 on mismatch)")
@@ -349,7 +357,7 @@ def main():
             d_last = all_gather_rows(d_last, n_total)
         dump = {"knn_scores": d_last.cpu().numpy().astype(np.float32), "knn_ids": i_last.cpu().numpy().astype(np.float64)}
     other = None
-    if world > 1:                                          # the other scaling mode, same run, reported as an extra key
+    if world > 1 and a.full:                               # the other scaling mode, same run, reported as an extra key
         if scaling == "strong":
             ostep, on = make_step(x_full, a.batch * world), a.batch * world
         else:
@@ -430,7 +438,7 @@ def main():
             line["encoder_mfma_frac_end_to_end"] = round(value / world * (FLOP_PER_CROP[a.arch] - pruned) / MFMA_PEAK[a.precision], 4)
             line["flop_per_crop"] = {"model": FLOP_PER_CROP[a.arch], "executed": FLOP_PER_CROP[a.arch] - pruned,
                                      "encoder_mfma_frac_at_model_flops": round(value / world * FLOP_PER_CROP[a.arch] / MFMA_PEAK[a.precision], 4)}
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             try:
                 line["precision"] = precision_extras(a, enc, knn, sd, dev, x_full, dom)
                 # the tolerance-meeting mode's roofline record at the top level (the driver keeps top-level roofline objects)
@@ -450,7 +458,7 @@ def main():
                     line["c5"] = c5_extras(a, dev)
             except Exception as e:                          # extras never take the headline down
                 line["extras_error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.arch, sd, index_cpu, a.k, a.cpu_seconds)
         if a.dump_outputs:
             write_outputs(a.dump_outputs, dump)

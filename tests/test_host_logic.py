@@ -420,6 +420,28 @@ def test_bench_dump_outputs_writer(tmp_path):
         sys.argv = argv
 
 
+def test_bench_full_is_opt_in():
+    """bench.py's options: --full (the extras, the CPU baseline and the other scaling mode) is off in a plain ``--gpus 1 --steps K
+    --warmup W`` run and leaves --steps / --warmup alone; --no-extras / --no-cpu-baseline still parse beside it to narrow a --full run."""
+    import importlib.util
+    import os
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "3"]
+        plain = mod.parse()
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"]
+        full = mod.parse()
+    finally:
+        sys.argv = argv
+    assert not plain.full and not plain.no_extras and not plain.no_cpu_baseline
+    assert full.full and full.no_cpu_baseline and not full.no_extras
+    assert (plain.steps, plain.warmup) == (full.steps, full.warmup) == (20, 3)
+
+
 def test_yolov5s_table_and_letterbox_geometry():
     """The layer table has ultralytics' published YOLOv5s (v6) size — 7,235,389 parameters at 80 classes ("YOLOv5s summary:
     270 layers, 7235389 parameters") — and letterbox_geometry is the arithmetic of localizer_engine.py:107-138."""

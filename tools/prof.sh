@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 20 --warmup 3 --breakdown $EXTRA $( [ -n "$EXTRA" ] && echo "--no-extras --no-cpu-baseline" ) > $OUT/bench.json 2> $OUT/bench_breakdown.txt
+python bench.py --full --steps 20 --warmup 3 --breakdown $EXTRA $( [ -n "$EXTRA" ] && echo "--no-extras --no-cpu-baseline" ) > $OUT/bench.json 2> $OUT/bench_breakdown.txt
 BENCH="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras $EXTRA"
 echo "$BENCH" > $OUT/cmd.txt
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats -- $BENCH > $OUT/stats.log 2>&1
