@@ -210,6 +210,64 @@ def head_lib():
     return _head
 
 
+# libeffocr_swin.so (include/effocr_swin.h): the Swin-T encoder, a library of its own for the same reason (it carries its own copy of
+# the GEMMs, hidden).  Bound by swin_lib(); its functions are not part of EXPORTS either.
+SWIN_SO_PATH = os.path.join(_HERE, "libeffocr_swin.so")
+SWIN_ABI_VERSION = 1     # == EFFOCR_SWIN_ABI_VERSION of include/effocr_swin.h
+_swin = None
+
+
+def _swin_signatures():
+    c = ctypes
+    vp, i32, i64, sz = c.c_void_p, c.c_int, c.c_int64, c.c_size_t
+    return {
+        "effocr_swin_abi_version": (i32, []),
+        "effocr_swin_last_error": (c.c_char_p, []),
+        "effocr_swin_create": (i32, [c.c_char_p, i32, i32, c.POINTER(vp)]),
+        "effocr_swin_destroy": (None, [vp]),
+        "effocr_swin_embed_dim": (i32, [vp]),
+        "effocr_swin_num_params": (i32, [vp]),
+        "effocr_swin_param_name": (c.c_char_p, [vp, i32]),
+        "effocr_swin_param_numel": (i64, [vp, i32]),
+        "effocr_swin_set_param": (i32, [vp, c.c_char_p, vp, i64]),
+        "effocr_swin_weights_bytes": (sz, [vp]),
+        "effocr_swin_upload": (i32, [vp, vp, sz]),
+        "effocr_swin_workspace_bytes": (sz, [vp, i32]),
+        "effocr_swin_set_chunk": (i32, [vp, i32]),
+        "effocr_swin_forward": (i32, [vp, vp, i32, vp, i32, vp, sz, vp]),
+        "effocr_swin_check_status": (i32, [vp, vp, vp]),
+    }
+
+
+SWIN_EXPORTS = tuple(sorted(_swin_signatures()))
+
+
+def swin_lib():
+    """Load (once) and return the ctypes handle of libeffocr_swin.so; raises if it is missing or its ABI version differs."""
+    global _swin
+    with _lock:
+        if _swin is None:
+            if not os.path.exists(SWIN_SO_PATH):
+                raise EffOCRHipError(f"{SWIN_SO_PATH} not found: the Swin encoder library is required (no CPU fallback). "
+                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
+            handle = ctypes.CDLL(SWIN_SO_PATH)
+            for name, (res, args) in _swin_signatures().items():
+                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
+                fn.restype, fn.argtypes = res, args
+            got = handle.effocr_swin_abi_version()
+            if got != SWIN_ABI_VERSION:
+                raise EffOCRHipError(f"libeffocr_swin.so ABI version {got} != {SWIN_ABI_VERSION} expected by this package: rebuild "
+                                     "(make -C effocr_amd/csrc)")
+            _swin = handle
+    return _swin
+
+
+def swin_check(rc, what=""):
+    if rc != 0:
+        msg = swin_lib().effocr_swin_last_error()
+        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
 def head_check(rc, what=""):
     if rc != 0:
         msg = head_lib().effocr_head_last_error()

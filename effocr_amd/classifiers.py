@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from . import weights as W
-from .encoders import DEFAULT_PRECISION, HipEncoder
+from .encoders import DEFAULT_PRECISION, make_encoder
 
 
 class HipClassifierHead:
@@ -134,7 +134,7 @@ def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECI
         @property
         def engine(self):
             if self._engine is None:
-                self._engine = HipEncoder(self.model_name, self._sd, img_size=img_size, precision=precision, device=self._device)
+                self._engine = make_encoder(self.model_name, self._sd, img_size=img_size, precision=precision, device=self._device)
             return self._engine
 
         @property

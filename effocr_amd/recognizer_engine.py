@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import weights as W
-from .encoders import DEFAULT_PRECISION, HipEncoder
+from .encoders import DEFAULT_PRECISION, make_encoder
 
 
 class _Lane:
@@ -50,7 +50,7 @@ class EffRecognizer:
         else:
             sd = W.load_checkpoint(model)
         self.arch = arch or W.infer_arch(sd)
-        self._eng_net = HipEncoder(self.arch, sd, img_size=img_size, precision=precision, device=device)
+        self._eng_net = make_encoder(self.arch, sd, img_size=img_size, precision=precision, device=device)
         # One instance is shared by N Python threads in the reference (infer_effocr_onnx_multi.py:207-223,350-364).
         # `lanes` calls can be in flight at once; further callers wait for a free lane.  ctypes releases the GIL during
         # the enqueue and torch releases it during copies / synchronisation, so the threads really overlap:

@@ -18,6 +18,14 @@ MobileNetV3 (``mobilenetv3_small_050``) is described by timm's arch-def strings 
 (``mobilenetv3_blocks``), from which the key names and shapes follow (``conv_stem``, ``bn1``,
 ``blocks.i.j.{conv_pw,bn1,conv_dw,bn2,se.conv_reduce,se.conv_expand,conv_pwl,bn3}``, ``conv_head``); the
 builder is pinned by the parameter counts of three widths (tests/test_mobilenetv3_host.py).
+
+Swin-T (``swin_tiny_patch4_window7_224``) key names follow timm's ``swin_transformer.py`` as of timm 0.9
+(``patch_embed.proj`` / ``patch_embed.norm``, ``layers.i.blocks.j.{norm1,attn.relative_position_bias_table,attn.qkv,attn.proj,
+norm2,mlp.fc1,mlp.fc2}``, the patch merging ``layers.i.downsample.{norm,reduction}`` at the START of stages 1-3, ``norm``, classifier
+``head.fc``).  Checkpoints of timm < 0.9 (patch merging at the END of stages 0-2, classifier ``head``) are renamed to that layout by
+``strip_prefix``, and the derived buffers ``relative_position_index`` / ``attn_mask`` are dropped.  timm is not installed here either:
+the names could not be checked against timm itself; the architecture and the shapes are pinned against ``transformers.SwinModel``
+(tests/test_swin_host.py).
 """
 from collections import OrderedDict
 import math
@@ -50,6 +58,10 @@ MOBILENETV3_ARCH_DEF = (
     ("ir_r3_k5_s2_e6_c96_se0.25",),
     ("cn_r1_k1_s1_c576",),
 )
+SWIN_CFG = {
+    # name: (embed_dim, depths, heads, window) — timm swin_transformer.py; head dim 32 in every stage, mlp ratio 4, patch 4
+    "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24), 7),
+}
 MOBILENETV3_FEATURES = 1024           # conv_head width (not scaled by the multiplier)
 PATCH = 16
 
@@ -113,7 +125,13 @@ def embed_dim(arch):
         return CONVNEXT_CFG[arch][1][-1]
     if arch in MOBILENETV3_CFG:
         return MOBILENETV3_FEATURES
+    if arch in SWIN_CFG:
+        return SWIN_CFG[arch][0] * 8
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def is_swin(arch):
+    return arch in SWIN_CFG
 
 
 def is_convnext(arch):
@@ -124,8 +142,10 @@ def is_convnext(arch):
 # (models/classifiers.py:35-83).  Its input is the encoder's embedding before L2 normalisation (HipEncoder.forward(x, normalize=False)):
 # resnet18 the global-pooled features, ViT norm(x)[:, 0] (fc_norm is Identity for token pooling), convnext_tiny the output of head.norm,
 # mobilenetv3 conv_head + hard-swish.
+# swin_tiny_patch4_window7_224: the mean of the final norm's tokens (timm >= 0.9 names the head head.fc; strip_prefix renames timm < 0.9's head).
 HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bias"),
-             "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias")}
+             "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias"),
+             "swin": ("head.fc.weight", "head.fc.bias")}
 
 
 def _family(arch):
@@ -137,6 +157,8 @@ def _family(arch):
         return "convnext"
     if arch in MOBILENETV3_CFG:
         return "mobilenetv3"
+    if arch in SWIN_CFG:
+        return "swin"
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -243,7 +265,44 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return s
     if arch in MOBILENETV3_CFG:
         return _mobilenetv3_shapes(arch)
+    if arch in SWIN_CFG:
+        return _swin_shapes(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _swin_shapes(arch):
+    """timm >= 0.9 state-dict order (a module's own parameters before its children's: the bias table before qkv / proj)."""
+    C0, depths, heads, ws = SWIN_CFG[arch]
+    s = OrderedDict()
+    s["patch_embed.proj.weight"] = (C0, 3, 4, 4)
+    s["patch_embed.proj.bias"] = (C0,)
+    s["patch_embed.norm.weight"] = (C0,)
+    s["patch_embed.norm.bias"] = (C0,)
+    for i, (nb, nh) in enumerate(zip(depths, heads)):
+        c = C0 << i
+        p = f"layers.{i}."
+        if i > 0:
+            s[p + "downsample.norm.weight"] = (2 * c,)    # LayerNorm over the 4 C_prev = 2 c gathered channels
+            s[p + "downsample.norm.bias"] = (2 * c,)
+            s[p + "downsample.reduction.weight"] = (c, 2 * c)
+        for j in range(nb):
+            q = p + f"blocks.{j}."
+            s[q + "norm1.weight"] = (c,)
+            s[q + "norm1.bias"] = (c,)
+            s[q + "attn.relative_position_bias_table"] = ((2 * ws - 1) ** 2, nh)
+            s[q + "attn.qkv.weight"] = (3 * c, c)
+            s[q + "attn.qkv.bias"] = (3 * c,)
+            s[q + "attn.proj.weight"] = (c, c)
+            s[q + "attn.proj.bias"] = (c,)
+            s[q + "norm2.weight"] = (c,)
+            s[q + "norm2.bias"] = (c,)
+            s[q + "mlp.fc1.weight"] = (4 * c, c)
+            s[q + "mlp.fc1.bias"] = (4 * c,)
+            s[q + "mlp.fc2.weight"] = (c, 4 * c)
+            s[q + "mlp.fc2.bias"] = (c,)
+    s["norm.weight"] = (C0 * 8,)
+    s["norm.bias"] = (C0 * 8,)
+    return s
 
 
 def _mobilenetv3_shapes(arch, num_classes=0):
@@ -321,6 +380,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_convnext(arch, seed, img_size, scale)
     if arch in MOBILENETV3_CFG:
         return _init_mobilenetv3(arch, seed, img_size, scale)
+    if arch in SWIN_CFG:
+        return _init_swin(arch, seed, img_size, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -445,6 +506,35 @@ def _init_mobilenetv3(arch, seed, img_size, scale):
     return sd
 
 
+def _init_swin(arch, seed, img_size, scale):
+    """Swin seeded init.  scale="timm": what timm's initialiser gives (trunc_normal(0.02) linears and bias tables, zero biases,
+    LayerNorms at identity).  scale="unit": fan-in-scaled linears and patch conv, LayerNorm gains U(0.5, 1.5), biases N(0, 0.1) and
+    bias tables N(0, 1) — a relative-position term as large as the scores, so a wrong index, mask or merge order shows."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    sd = OrderedDict()
+
+    def randn(shape, std):
+        return torch.randn(shape, generator=g, dtype=torch.float32) * std
+
+    for k, shp in param_shapes(arch, img_size).items():
+        leaf = k.rsplit(".", 1)[-1]
+        is_ln = ".norm" in k or k.startswith("norm.") or "patch_embed.norm." in k
+        if leaf == "relative_position_bias_table":
+            v = randn(shp, 0.02).clamp_(-0.04, 0.04) if scale == "timm" else randn(shp, 1.0)
+        elif len(shp) == 1:
+            if scale == "timm":
+                v = torch.ones(shp) if (leaf == "weight" and is_ln) else torch.zeros(shp)
+            else:
+                v = torch.rand(shp, generator=g) + 0.5 if (leaf == "weight" and is_ln) else randn(shp, 0.1)
+        elif scale == "timm":
+            v = randn(shp, 0.02).clamp_(-0.04, 0.04)
+        else:
+            v = randn(shp, 1.0 / math.sqrt(math.prod(shp[1:])))
+        sd[k] = v.contiguous()
+    return sd
+
+
 def init_head(arch, num_classes, seed=0, scale="unit"):
     """Seeded classifier head from a CPU Philox generator of its own (seeded from ``seed`` and the tag 0x68656164): scale="unit"
     gives weights N(0, 1/D) and biases N(0, 0.1), so logits are O(1) for O(1) embeddings; scale="timm" gives timm's
@@ -472,11 +562,35 @@ def infer_num_classes(sd):
 
 
 def strip_prefix(sd, prefix="net."):
-    """models/encoders.py:60 keeps the timm module as ``self.net`` -> keys ``net.<timm key>``."""
+    """models/encoders.py:60 keeps the timm module as ``self.net`` -> keys ``net.<timm key>``.  A Swin state dict also comes out in
+    timm >= 0.9's layout (swin_canonical); every other state dict only loses the prefix."""
     keys = list(sd.keys())
     if keys and all(k.startswith(prefix) for k in keys):
-        return OrderedDict((k[len(prefix):], v) for k, v in sd.items())
-    return OrderedDict(sd)
+        sd = OrderedDict((k[len(prefix):], v) for k, v in sd.items())
+    return swin_canonical(sd) if "layers.0.blocks.0.attn.relative_position_bias_table" in sd else OrderedDict(sd)
+
+
+_SWIN_OLD_DOWNSAMPLE = re.compile(r"^layers\.(\d+)\.downsample\.")
+
+
+def swin_canonical(sd):
+    """A Swin state dict in timm >= 0.9's layout.  timm < 0.9 keeps the patch merging at the END of stages 0-2 (``layers.i.downsample``,
+    i = 0..2) and names the classifier ``head``; timm >= 0.9 keeps it at the START of stages 1-3 and names the classifier ``head.fc``.
+    The layouts are told apart by the downsample indices (a ``layers.0.downsample`` exists only in the old one).  The derived buffers
+    ``relative_position_index`` and ``attn_mask`` are dropped: the kernels compute both from the geometry."""
+    old = any(k.startswith("layers.0.downsample.") for k in sd)
+    out = OrderedDict()
+    for k, v in sd.items():
+        if k.endswith((".relative_position_index", ".attn_mask")):
+            continue
+        if old:
+            m = _SWIN_OLD_DOWNSAMPLE.match(k)
+            if m:
+                k = f"layers.{int(m.group(1)) + 1}.downsample." + k[m.end():]
+            elif k in ("head.weight", "head.bias"):
+                k = "head.fc." + k[len("head."):]
+        out[k] = v
+    return out
 
 
 def load_checkpoint(path):
@@ -522,6 +636,11 @@ def infer_arch(sd):
                        for i in range(4))
         for name, (dep, wid) in CONVNEXT_CFG.items():
             if dep == depths and wid == widths:
+                return name
+    if "patch_embed.proj.weight" in sd and "layers.0.blocks.0.attn.relative_position_bias_table" in sd:
+        for name in SWIN_CFG:
+            want = param_shapes(name)
+            if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
                 return name
     if "conv_stem.weight" in sd and "conv_head.weight" in sd:
         for name in MOBILENETV3_CFG:
