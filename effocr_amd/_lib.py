@@ -262,6 +262,46 @@ def swin_lib():
     return _swin
 
 
+# libeffocr_resnet.so (include/effocr_resnet.h): the ResNet-34 / ResNet-50 encoders, a library of its own for the same reason (it carries its
+# own copy of resnet18's fp32 convolution pipeline, hidden).  Bound by resnet_lib(); its functions are not part of EXPORTS either.
+RESNET_SO_PATH = os.path.join(_HERE, "libeffocr_resnet.so")
+RESNET_ABI_VERSION = 1     # == EFFOCR_RESNET_ABI_VERSION of include/effocr_resnet.h
+_resnet = None
+
+
+def _resnet_signatures():
+    return {k.replace("effocr_swin_", "effocr_resnet_"): v for k, v in _swin_signatures().items()}
+
+
+RESNET_EXPORTS = tuple(sorted(_resnet_signatures()))
+
+
+def resnet_lib():
+    """Load (once) and return the ctypes handle of libeffocr_resnet.so; raises if it is missing or its ABI version differs."""
+    global _resnet
+    with _lock:
+        if _resnet is None:
+            if not os.path.exists(RESNET_SO_PATH):
+                raise EffOCRHipError(f"{RESNET_SO_PATH} not found: the ResNet encoder library is required (no CPU fallback). "
+                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
+            handle = ctypes.CDLL(RESNET_SO_PATH)
+            for name, (res, args) in _resnet_signatures().items():
+                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
+                fn.restype, fn.argtypes = res, args
+            got = handle.effocr_resnet_abi_version()
+            if got != RESNET_ABI_VERSION:
+                raise EffOCRHipError(f"libeffocr_resnet.so ABI version {got} != {RESNET_ABI_VERSION} expected by this package: rebuild "
+                                     "(make -C effocr_amd/csrc)")
+            _resnet = handle
+    return _resnet
+
+
+def resnet_check(rc, what=""):
+    if rc != 0:
+        msg = resnet_lib().effocr_resnet_last_error()
+        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
 def swin_check(rc, what=""):
     if rc != 0:
         msg = swin_lib().effocr_swin_last_error()

@@ -1,0 +1,367 @@
+// C ABI of libeffocr_resnet.so (include/effocr_resnet.h): the ResNet-34 / ResNet-50 encoder handle (parameter table, host-side BN folding
+// and packing, sub-batched forward orchestration) and the library's own error state.  The 16-bit modes run resnet16.hip's kernels; the
+// fp32 mode runs the exact-fp32 convolution pipeline of resnet.hip, which this library compiles a second time with hidden visibility, with
+// its split-K turned off.  All device memory is caller-owned; this file allocates host memory only.
+#include "../../include/effocr_resnet.h"
+#include "common.hpp"
+#include "kernels.hpp"
+#include "resnet16.hpp"
+
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#define RESNET_API extern "C" __attribute__((visibility("default")))
+
+namespace effocr {
+
+// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
+static thread_local std::string g_resnet_err;
+void set_error(const std::string& msg) { g_resnet_err = msg; }
+int fail(int code, const std::string& msg) { g_resnet_err = msg; return code; }
+int check_launch(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return EFFOCR_OK;
+}
+int device_cus() {
+  static int cache[64] = {0};                            // benign race: every thread computes the same value
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cache[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    cache[dev] = v;
+  }
+  return cache[dev];
+}
+
+namespace {
+
+// sub-batches: as many crops as keep the workspace under RN_WS_BUDGET (1 GB < 1 GiB), at most RN_MAX_CHUNK
+constexpr size_t RN_WS_BUDGET = (size_t)1000 << 20;
+constexpr int RN_MAX_CHUNK = 256;
+constexpr int RN_STEM_K32 = 160;   // fp32 stem im2col columns (resnet.hip's im2col_conv1: 147 taps padded to 5 K-stages of 32)
+
+struct Param { std::string name; int64_t numel; std::vector<float> data; bool set; };
+// one convolution + its BatchNorm: timm key prefixes, geometry and blob offsets (weights [cout][kpad], bias [cout] fp32)
+struct Conv { std::string w, bn; int cin, cout, k, stride, pad, kpad; size_t w_off, b_off; };
+// one residual block: convs[c0 ..] = conv1, conv2 (, conv3) (, downsample)
+struct Block { int c0, nconv, stride; bool down; };
+
+struct Alloc {
+  size_t off = 0;
+  size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
+
+uint16_t f32_to_bf16(float f) {
+  uint32_t u; memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
+  u += 0x7fffu + ((u >> 16) & 1u);                                            // round to nearest even
+  return (uint16_t)(u >> 16);
+}
+uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
+
+}  // namespace
+}  // namespace effocr
+
+using namespace effocr;
+
+struct effocr_resnet {
+  int img = 224, prec = PREC_FP16, D = 0, chunk = 0;
+  bool bottleneck = false;
+  std::vector<Param> params;
+  std::map<std::string, int> index;
+  std::vector<Conv> convs;          // conv1 (stem), then the blocks' convolutions in forward order
+  std::vector<Block> blocks;
+  size_t wbytes = 0;
+  const char* wdev = nullptr;
+};
+
+namespace effocr {
+namespace {
+
+void add_param(effocr_resnet* e, const std::string& name, int64_t numel) {
+  e->index[name] = (int)e->params.size();
+  e->params.push_back(Param{name, numel, {}, false});
+}
+void add_bn(effocr_resnet* e, const std::string& p, int c) {
+  add_param(e, p + ".weight", c); add_param(e, p + ".bias", c);
+  add_param(e, p + ".running_mean", c); add_param(e, p + ".running_var", c);
+}
+void add_conv(effocr_resnet* e, const std::string& w, const std::string& bn, int cin, int cout, int k, int stride, int pad) {
+  add_param(e, w, (int64_t)cout * cin * k * k);
+  add_bn(e, bn, cout);
+  e->convs.push_back(Conv{w, bn, cin, cout, k, stride, pad, k * k * cin, 0, 0});
+}
+
+const std::vector<float>& P(const effocr_resnet* e, const std::string& n) { return e->params[e->index.at(n)].data; }
+
+// timm resnet34 (BasicBlock) / resnet50 (Bottleneck): depths 3-4-6-3, widths 64-128-256-512 (x4 expansion for the bottleneck),
+// 7x7/2 stem + 3x3/2 max pool, the stride on the 3x3 conv (the bottleneck's conv2), a 1x1 stride-s conv + BN shortcut, BN eps 1e-5.
+void build_resnet(effocr_resnet* e) {
+  static const int depths[4] = {3, 4, 6, 3}, widths[4] = {64, 128, 256, 512};
+  const int exp = e->bottleneck ? 4 : 1;
+  add_conv(e, "conv1.weight", "bn1", 3, 64, 7, 2, 3);
+  e->convs[0].kpad = e->prec == PREC_FP32 ? RN_STEM_K32 : RN_STEM_K16;
+  int cin = 64;
+  for (int li = 0; li < 4; ++li) {
+    const int w = widths[li], cout = w * exp;
+    for (int bi = 0; bi < depths[li]; ++bi) {
+      const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(bi) + ".";
+      const int stride = (bi == 0 && li > 0) ? 2 : 1;
+      Block b{(int)e->convs.size(), 0, stride, bi == 0 && (stride != 1 || cin != cout)};
+      if (e->bottleneck) {
+        add_conv(e, p + "conv1.weight", p + "bn1", cin, w, 1, 1, 0);
+        add_conv(e, p + "conv2.weight", p + "bn2", w, w, 3, stride, 1);
+        add_conv(e, p + "conv3.weight", p + "bn3", w, cout, 1, 1, 0);
+      } else {
+        add_conv(e, p + "conv1.weight", p + "bn1", cin, w, 3, stride, 1);
+        add_conv(e, p + "conv2.weight", p + "bn2", w, w, 3, 1, 1);
+      }
+      if (b.down) add_conv(e, p + "downsample.0.weight", p + "downsample.1", cin, cout, 1, stride, 0);
+      b.nconv = (int)e->convs.size() - b.c0;
+      e->blocks.push_back(b);
+      cin = cout;
+    }
+  }
+  e->D = cin;
+  const size_t es = prec_esize(e->prec);
+  Alloc a;
+  for (Conv& c : e->convs) {
+    c.w_off = a.take((size_t)c.cout * c.kpad * es);
+    c.b_off = a.take((size_t)c.cout * 4);
+  }
+  e->wbytes = a.off;
+}
+
+// BatchNorm (eval, eps 1e-5) folded into the conv in double: w' = w * g/sqrt(v+eps), b' = beta - mean*g/sqrt(v+eps); the weight re-laid-out
+// from torch [Cout,Cin,KH,KW] to [Cout][KH][KW][Cin] (Cin fastest), zero-padded to kpad columns, then rounded once to the operand type.
+void pack_resnet(const effocr_resnet* e, std::vector<char>& blob) {
+  for (const Conv& c : e->convs) {
+    const auto& w = P(e, c.w);
+    const auto& g = P(e, c.bn + ".weight"); const auto& bt = P(e, c.bn + ".bias");
+    const auto& mu = P(e, c.bn + ".running_mean"); const auto& var = P(e, c.bn + ".running_var");
+    std::vector<float> wd((size_t)c.cout * c.kpad, 0.f);
+    float* bd = reinterpret_cast<float*>(blob.data() + c.b_off);
+    for (int co = 0; co < c.cout; ++co) {
+      const double sc = (double)g[co] / sqrt((double)var[co] + 1e-5);
+      bd[co] = (float)((double)bt[co] - (double)mu[co] * sc);
+      for (int ky = 0; ky < c.k; ++ky)
+        for (int kx = 0; kx < c.k; ++kx)
+          for (int cc = 0; cc < c.cin; ++cc) {
+            const float v = w[(((size_t)co * c.cin + cc) * c.k + ky) * c.k + kx];
+            wd[(size_t)co * c.kpad + (ky * c.k + kx) * c.cin + cc] = (float)((double)v * sc);
+          }
+    }
+    if (e->prec == PREC_FP32) { memcpy(blob.data() + c.w_off, wd.data(), wd.size() * 4); continue; }
+    uint16_t* d = reinterpret_cast<uint16_t*>(blob.data() + c.w_off);
+    for (size_t i = 0; i < wd.size(); ++i) d[i] = e->prec == PREC_BF16 ? f32_to_bf16(wd[i]) : f32_to_f16(wd[i]);
+  }
+}
+
+// Workspace of one sub-batch of B crops: the status word and four activation buffers, each as large as the largest activation (the stem's
+// output, S/2 x S/2 x 64, equals resnet50's layer1 output S/4 x S/4 x 256).  The stem's im2col rows overlay buffers 1-3, which are free
+// until the max pool.
+struct RnWs { size_t status, buf[4], total; };
+RnWs resnet_ws(const effocr_resnet* e, int B) {
+  const size_t es = prec_esize(e->prec);
+  const size_t s2 = (size_t)(e->img / 2) * (e->img / 2);
+  const size_t act = align_up((size_t)B * s2 * 64 * es, 256);
+  const size_t col = (size_t)B * s2 * e->convs[0].kpad * es;
+  Alloc a; RnWs w;
+  w.status = a.take(256);                   // int32 status word at workspace offset 0 (effocr_resnet_check_status)
+  w.buf[0] = a.take(act);
+  const size_t rest = a.take(std::max(3 * act, col));
+  for (int i = 1; i < 4; ++i) w.buf[i] = rest + (size_t)(i - 1) * act;
+  w.total = a.off;
+  return w;
+}
+
+int resnet_chunk(const effocr_resnet* e, int batch) {
+  int c = e->chunk;
+  if (c <= 0) c = (int)std::min<size_t>(RN_MAX_CHUNK, std::max<size_t>(1, RN_WS_BUDGET / resnet_ws(e, 1).total));
+  return c < batch ? c : batch;
+}
+
+// one convolution (+ folded BN) with the epilogue: + residual, ReLU.  16-bit modes: resnet16.hip's kernel; fp32: resnet.hip's with no
+// split-K scratch (its split count would depend on the number of output pixels, i.e. on the call size).
+int conv(const effocr_resnet* e, const Conv& c, const void* in, int B, int H, int W, int OH, int OW, const void* resid, int relu, void* out,
+         hipStream_t s) {
+  const char* wb = e->wdev;
+  if (e->prec == PREC_FP32) {
+    ConvArgs a{};
+    a.in = static_cast<const float*>(in); a.w = reinterpret_cast<const float*>(wb + c.w_off);
+    a.bias = reinterpret_cast<const float*>(wb + c.b_off); a.resid = static_cast<const float*>(resid); a.out = static_cast<float*>(out);
+    a.B = B; a.H = H; a.W = W; a.Cin = c.kpad / (c.k * c.k); a.Cout = c.cout; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
+    a.OH = OH; a.OW = OW; a.relu = relu;
+    return conv2d_nhwc(a, s);
+  }
+  Conv16Args a{};
+  a.in = in; a.w = wb + c.w_off; a.bias = reinterpret_cast<const float*>(wb + c.b_off); a.resid = resid; a.out = out;
+  a.B = B; a.H = H; a.W = W; a.Cin = c.kpad / (c.k * c.k); a.Cout = c.cout; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
+  a.OH = OH; a.OW = OW; a.relu = relu;
+  return rn_conv16(e->prec, a, s);
+}
+
+// One sub-batch: stem (im2col + 1x1 GEMM, bn1, ReLU) -> max pool -> 16 residual blocks -> global average pool (+ F.normalize).
+int resnet_forward(const effocr_resnet* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
+  const RnWs w = resnet_ws(e, B);
+  const bool f32 = e->prec == PREC_FP32;
+  void* buf[4];
+  for (int i = 0; i < 4; ++i) buf[i] = ws + w.buf[i];
+  int* status = reinterpret_cast<int*>(ws + w.status);
+  int rc;
+  int H = e->img, OH = H / 2;
+  void* col = buf[1];
+  if ((rc = f32 ? im2col_conv1(x, static_cast<float*>(col), B, H, H, OH, OH, s) : rn_im2col16(e->prec, x, col, B, H, H, OH, OH, s))) return rc;
+  // the stem's im2col rows as a 1x1 convolution over B*OH*OH "images" of one pixel
+  Conv stem = e->convs[0];
+  stem.k = 1; stem.stride = 1; stem.pad = 0;
+  if ((rc = conv(e, stem, col, B * OH * OH, 1, 1, 1, 1, nullptr, 1, buf[0], s))) return rc;
+  H = OH; OH = (H - 1) / 2 + 1;
+  if ((rc = f32 ? maxpool3x3s2_nhwc(static_cast<float*>(buf[0]), static_cast<float*>(buf[1]), B, H, H, 64, OH, OH, s)
+                : rn_maxpool16(e->prec, buf[0], buf[1], B, H, H, 64, OH, OH, s))) return rc;
+  H = OH;
+  int cur = 1;                                          // buf[cur] holds the block input
+  for (const Block& b : e->blocks) {
+    int t[3], n = 0;
+    for (int i = 0; i < 4; ++i) if (i != cur) t[n++] = i;
+    const int Ho = (H - 1) / b.stride + 1;
+    const Conv* cv = e->convs.data() + b.c0;
+    const void* idt = buf[cur];
+    if (b.down) {                                       // shortcut: 1x1 stride-s conv + BN into t[2]
+      if ((rc = conv(e, cv[b.nconv - 1], buf[cur], B, H, H, Ho, Ho, nullptr, 0, buf[t[2]], s))) return rc;
+      idt = buf[t[2]];
+    }
+    int out;
+    if (e->bottleneck) {                                // 1x1 -> t0, 3x3/s -> t1, 1x1 + identity -> t0
+      if ((rc = conv(e, cv[0], buf[cur], B, H, H, H, H, nullptr, 1, buf[t[0]], s))) return rc;
+      if ((rc = conv(e, cv[1], buf[t[0]], B, H, H, Ho, Ho, nullptr, 1, buf[t[1]], s))) return rc;
+      if ((rc = conv(e, cv[2], buf[t[1]], B, Ho, Ho, Ho, Ho, idt, 1, buf[t[0]], s))) return rc;
+      out = t[0];
+    } else {                                            // 3x3/s -> t0, 3x3 + identity -> t1
+      if ((rc = conv(e, cv[0], buf[cur], B, H, H, Ho, Ho, nullptr, 1, buf[t[0]], s))) return rc;
+      if ((rc = conv(e, cv[1], buf[t[0]], B, Ho, Ho, Ho, Ho, idt, 1, buf[t[1]], s))) return rc;
+      out = t[1];
+    }
+    cur = out;
+    H = Ho;
+  }
+  return rn_avgpool(e->prec, buf[cur], emb, B, H * H, e->D, l2, status, s);
+}
+
+hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
+
+}  // namespace
+}  // namespace effocr
+
+RESNET_API int effocr_resnet_abi_version(void) { return EFFOCR_RESNET_ABI_VERSION; }
+RESNET_API const char* effocr_resnet_last_error(void) { return effocr::g_resnet_err.c_str(); }
+
+RESNET_API int effocr_resnet_create(const char* arch, int img_size, int precision, effocr_resnet_t** out) {
+  if (!arch || !out) return fail(EFFOCR_RESNET_EINVAL, "resnet_create: NULL argument");
+  if (precision < 0 || precision > 2) return fail(EFFOCR_RESNET_EINVAL, "resnet_create: unknown precision");
+  const std::string a = arch;
+  if (a != "resnet34" && a != "resnet50")
+    return fail(EFFOCR_RESNET_EUNSUPPORTED, "resnet_create: unsupported architecture '" + a + "' (resnet34, resnet50)");
+  if (img_size < 32 || img_size % 32) return fail(EFFOCR_RESNET_EINVAL, "resnet_create: img_size must be a positive multiple of 32");
+  std::unique_ptr<effocr_resnet> e(new effocr_resnet());
+  e->img = img_size; e->prec = precision; e->bottleneck = a == "resnet50";
+  build_resnet(e.get());
+  *out = e.release();
+  return EFFOCR_RESNET_OK;
+}
+
+RESNET_API void effocr_resnet_destroy(effocr_resnet_t* enc) { delete enc; }
+RESNET_API int effocr_resnet_embed_dim(const effocr_resnet_t* enc) { return enc ? enc->D : 0; }
+RESNET_API int effocr_resnet_num_params(const effocr_resnet_t* enc) { return enc ? (int)enc->params.size() : 0; }
+RESNET_API const char* effocr_resnet_param_name(const effocr_resnet_t* enc, int i) {
+  if (!enc || i < 0 || i >= (int)enc->params.size()) return nullptr;
+  return enc->params[i].name.c_str();
+}
+RESNET_API int64_t effocr_resnet_param_numel(const effocr_resnet_t* enc, int i) {
+  if (!enc || i < 0 || i >= (int)enc->params.size()) return -1;
+  return enc->params[i].numel;
+}
+
+RESNET_API int effocr_resnet_set_param(effocr_resnet_t* enc, const char* name, const float* host, int64_t numel) {
+  if (!enc || !name || !host) return fail(EFFOCR_RESNET_EINVAL, "resnet_set_param: NULL argument");
+  auto it = enc->index.find(name);
+  if (it == enc->index.end()) return fail(EFFOCR_RESNET_EINVAL, std::string("resnet_set_param: unknown parameter '") + name + "'");
+  Param& p = enc->params[it->second];
+  if (p.numel != numel)
+    return fail(EFFOCR_RESNET_EINVAL, std::string("resnet_set_param: '") + name + "' expects " + std::to_string(p.numel) +
+                                          " elements, got " + std::to_string(numel));
+  p.data.assign(host, host + numel);
+  p.set = true;
+  return EFFOCR_RESNET_OK;
+}
+
+RESNET_API size_t effocr_resnet_weights_bytes(const effocr_resnet_t* enc) { return enc ? enc->wbytes : 0; }
+
+RESNET_API int effocr_resnet_upload(effocr_resnet_t* enc, void* weights_dev, size_t bytes) {
+  if (!enc || !weights_dev) return fail(EFFOCR_RESNET_EINVAL, "resnet_upload: NULL argument");
+  if (bytes < enc->wbytes) return fail(EFFOCR_RESNET_EWORKSPACE, "resnet_upload: weight buffer too small");
+  for (const Param& p : enc->params)
+    if (!p.set) return fail(EFFOCR_RESNET_ESTATE, "resnet_upload: parameter '" + p.name + "' was never set");
+  std::vector<char> blob(enc->wbytes, 0);
+  pack_resnet(enc, blob);
+  const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
+  if (er != hipSuccess) return fail(EFFOCR_RESNET_EHIP, std::string("resnet_upload: hipMemcpy: ") + hipGetErrorString(er));
+  enc->wdev = static_cast<const char*>(weights_dev);
+  return EFFOCR_RESNET_OK;
+}
+
+RESNET_API size_t effocr_resnet_workspace_bytes(const effocr_resnet_t* enc, int batch) {
+  if (!enc || batch <= 0) return 0;
+  return resnet_ws(enc, resnet_chunk(enc, batch)).total;
+}
+
+RESNET_API int effocr_resnet_set_chunk(effocr_resnet_t* enc, int crops_per_chunk) {
+  if (!enc || crops_per_chunk < 0) return fail(EFFOCR_RESNET_EINVAL, "resnet_set_chunk: bad argument");
+  enc->chunk = crops_per_chunk;
+  return EFFOCR_RESNET_OK;
+}
+
+RESNET_API int effocr_resnet_forward(effocr_resnet_t* enc, const float* x_dev, int batch, float* emb_dev, int l2_normalize,
+                                     void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (!enc) return fail(EFFOCR_RESNET_EINVAL, "resnet_forward: NULL encoder");
+  if (batch < 0) return fail(EFFOCR_RESNET_EINVAL, "resnet_forward: negative batch");
+  if (batch == 0) return EFFOCR_RESNET_OK;
+  if (!x_dev || !emb_dev || !workspace_dev) return fail(EFFOCR_RESNET_EINVAL, "resnet_forward: NULL device pointer");
+  if (!enc->wdev) return fail(EFFOCR_RESNET_ESTATE, "resnet_forward: weights were not uploaded");
+  if (workspace_bytes < effocr_resnet_workspace_bytes(enc, batch)) return fail(EFFOCR_RESNET_EWORKSPACE, "resnet_forward: workspace too small");
+  const int chunk = resnet_chunk(enc, batch);
+  const int64_t s2 = (int64_t)(enc->img / 2) * (enc->img / 2);
+  if ((int64_t)chunk * s2 * enc->convs[0].kpad >= (int64_t)1 << 31)
+    return fail(EFFOCR_RESNET_EUNSUPPORTED, "resnet_forward: chunk too large for 32-bit activation indices (effocr_resnet_set_chunk)");
+  char* ws = static_cast<char*>(workspace_dev);
+  const size_t img_elems = (size_t)3 * enc->img * enc->img;
+  // every kernel reads and writes its own crops' pixels only: the embeddings are bit-identical for every chunk setting
+  for (int b0 = 0; b0 < batch; b0 += chunk) {
+    const int cb = std::min(chunk, batch - b0);
+    const int rc = resnet_forward(enc, x_dev + (size_t)b0 * img_elems, cb, emb_dev + (size_t)b0 * enc->D, l2_normalize, ws, S(stream));
+    if (rc) return rc;
+  }
+  return EFFOCR_RESNET_OK;
+}
+
+RESNET_API int effocr_resnet_check_status(const effocr_resnet_t* enc, const void* workspace_dev, void* stream) {
+  if (!enc || !workspace_dev) return fail(EFFOCR_RESNET_EINVAL, "resnet_check_status: NULL argument");
+  int st = 0;
+  hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // RnWs::status = offset 0
+  if (er == hipSuccess) er = hipStreamSynchronize(S(stream));
+  if (er == hipSuccess && st != 0) er = hipMemsetAsync(const_cast<void*>(workspace_dev), 0, sizeof(int), S(stream));   // read-and-clear
+  if (er != hipSuccess) return fail(EFFOCR_RESNET_EHIP, std::string("resnet_check_status: ") + hipGetErrorString(er));
+  if (st != 0)
+    return fail(EFFOCR_RESNET_EOVERFLOW, enc->prec == PREC_FP16
+                    ? "forward: non-finite embedding — an f16 activation overflowed (beyond 65504) or the input was not finite; use "
+                      "precision bf16 or fp32 for this checkpoint"
+                    : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
+  return EFFOCR_RESNET_OK;
+}

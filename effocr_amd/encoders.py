@@ -346,18 +346,98 @@ class SwinEncoder(HipEncoder):
         raise NotImplementedError("the Swin encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
 
 
+class ResNetEncoder(HipEncoder):
+    """HipEncoder's interface over libeffocr_resnet.so (include/effocr_resnet.h): resnet34 / resnet50 at any img_size that is a positive
+    multiple of 32, fp32 crops in every precision mode (the stem's im2col reads them and rounds to the operand type).  Same per-stream
+    grow-only workspaces with their sticky status word; no stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
+
+    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
+        if precision not in _lib.PREC:
+            raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
+        self.device = _lib.require_gpu(device)
+        self.arch, self.img_size, self.precision = arch, int(img_size), precision
+        self._L = _lib.resnet_lib()
+        self._lock = threading.Lock()
+        self._h = ctypes.c_void_p()
+        _lib.resnet_check(self._L.effocr_resnet_create(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)),
+                          "effocr_resnet_create")
+        self.embed_dim = int(self._L.effocr_resnet_embed_dim(self._h))
+        sd = W.strip_prefix(state_dict)
+        W.check_state_dict(arch, sd, self.img_size)
+        for i in range(self._L.effocr_resnet_num_params(self._h)):
+            name = self._L.effocr_resnet_param_name(self._h, i).decode()
+            t = sd[name].detach().to("cpu", torch.float32).contiguous()
+            _lib.resnet_check(self._L.effocr_resnet_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()),
+                              f"effocr_resnet_set_param({name})")
+        nbytes = int(self._L.effocr_resnet_weights_bytes(self._h))
+        with torch.cuda.device(self.device):
+            self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.resnet_check(self._L.effocr_resnet_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_resnet_upload")
+        self._ws = {}
+        self.split_streams = False
+        self._side = None
+        self._side_used = set()
+        self._stream_locks = {}
+        self._profiling = False
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and self._h.value:
+                self._L.effocr_resnet_destroy(self._h)
+                self._h = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def set_chunk(self, crops_per_chunk):
+        """Internal sub-batch size (0 = the library's default: a workspace under 1 GB, at most 256 crops); effocr_resnet_set_chunk."""
+        _lib.resnet_check(self._L.effocr_resnet_set_chunk(self._h, int(crops_per_chunk)), "effocr_resnet_set_chunk")
+
+    def set_option(self, name, value):
+        raise ValueError(f"the ResNet-34/50 encoder has no option {name!r}")
+
+    def workspace_bytes(self, batch):
+        return int(self._L.effocr_resnet_workspace_bytes(self._h, int(batch)))
+
+    @property
+    def crop_dtype(self):
+        return torch.float32
+
+    def _enqueue(self, x, emb, normalize, ws):
+        _lib.resnet_check(self._L.effocr_resnet_forward(self._h, _lib.ptr(x), x.shape[0], _lib.ptr(emb), 1 if normalize else 0,
+                                                        _lib.ptr(ws), ws.numel(), _lib.current_stream(self.device)), "effocr_resnet_forward")
+
+    def check_status(self):
+        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
+        non-finite embedding (the status word is sticky; this call clears it)."""
+        with self._lock, torch.cuda.device(self.device):
+            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
+            if ws is None:
+                return
+            _lib.resnet_check(self._L.effocr_resnet_check_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
+                              "effocr_resnet_check_status")
+
+    def profile_begin(self, only=None):
+        raise NotImplementedError("the ResNet-34/50 encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+
+    def profile_collect(self):
+        raise NotImplementedError("the ResNet-34/50 encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+
+
 def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
-    """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, HipEncoder (libeffocr_hip.so) for every other architecture."""
-    cls = SwinEncoder if W.is_swin(arch) else HipEncoder
+    """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, ResNetEncoder (libeffocr_resnet.so) for resnet34 / resnet50,
+    HipEncoder (libeffocr_hip.so) for every other architecture."""
+    cls = SwinEncoder if W.is_swin(arch) else ResNetEncoder if W.is_resnet_lib(arch) else HipEncoder
     return cls(arch, state_dict, img_size=img_size, precision=precision, device=device)
 
 
 def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size=224):
     """Drop-in for models/encoders.py:50 ``AutoEncoderFactory(backend, modelpath)``.
 
-    Only the ``"timm"`` backend with the architectures BASELINE.json names, ``convnext_tiny`` and ``mobilenetv3_small_050``
-    (recommended by the reference README for ``--auto_model_timm``) and ``swin_tiny_patch4_window7_224`` is implemented (the "hf" branch and XcitDinoEncoder are out of scope); anything else raises
-    NotImplementedError exactly like the reference's ``else`` branch (encoders.py:93-95).
+    Only the ``"timm"`` backend is implemented, with the architectures BASELINE.json names (resnet18, vit_small_patch16_224,
+    vit_base_patch16_224), ``convnext_tiny`` and ``mobilenetv3_small_050`` (recommended by the reference README for
+    ``--auto_model_timm``), ``swin_tiny_patch4_window7_224``, ``resnet34`` and ``resnet50`` (the "hf" branch and XcitDinoEncoder are out
+    of scope); anything else raises NotImplementedError exactly like the reference's ``else`` branch
+    (encoders.py:93-95).
     ``precision`` / ``img_size`` are extensions with reference-compatible defaults.
     """
     if backend != "timm":

@@ -3,7 +3,7 @@
 The reference obtains its encoder from ``timm.create_model(name, num_classes=0)`` and saves /
 loads it as a torch state dict whose keys carry a ``net.`` prefix (models/encoders.py:56-70,
 train_effocr_recognizer.py:65-72).  This module knows the parameter names and shapes of the three
-architectures BASELINE.json names (resnet18, vit_small_patch16_224, vit_base_patch16_224) and of
+architectures BASELINE.json names (resnet18, vit_small_patch16_224, vit_base_patch16_224), of resnet34 / resnet50 and of
 convnext_tiny (one of the three encoders the reference README recommends for ``--auto_model_timm``)
 so that a real ``enc_best.pth`` drops in, and it produces the seeded random-init weights the
 benchmark and the tests use (there is no network for checkpoints).
@@ -38,7 +38,13 @@ VIT_CFG = {
     "vit_base_patch16_224": (768, 12, 12, 4),
     "vit_tiny_test": (128, 2, 2, 4),          # miniature used only by fast tests
 }
-RESNET_CFG = {"resnet18": ((2, 2, 2, 2), (64, 128, 256, 512))}
+RESNET_CFG = {
+    # name: (depths, widths, block) — timm resnet.py: "basic" = BasicBlock (two 3x3 convs), "bottleneck" = Bottleneck (1x1, 3x3 with the
+    # stride, 1x1 to 4 x width); 7x7/2 stem + 3x3/2 max pool, a 1x1 stride-s conv + BN shortcut where the shape changes, BN eps 1e-5
+    "resnet18": ((2, 2, 2, 2), (64, 128, 256, 512), "basic"),
+    "resnet34": ((3, 4, 6, 3), (64, 128, 256, 512), "basic"),
+    "resnet50": ((3, 4, 6, 3), (64, 128, 256, 512), "bottleneck"),
+}
 CONVNEXT_CFG = {
     # name: (depths, widths) — timm convnext.py; convnext_small would be ((3, 3, 27, 3), (96, 192, 384, 768))
     "convnext_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
@@ -120,7 +126,7 @@ def embed_dim(arch):
     if arch in VIT_CFG:
         return VIT_CFG[arch][0]
     if arch in RESNET_CFG:
-        return RESNET_CFG[arch][1][-1]
+        return RESNET_CFG[arch][1][-1] * resnet_expansion(arch)
     if arch in CONVNEXT_CFG:
         return CONVNEXT_CFG[arch][1][-1]
     if arch in MOBILENETV3_CFG:
@@ -132,6 +138,16 @@ def embed_dim(arch):
 
 def is_swin(arch):
     return arch in SWIN_CFG
+
+
+def resnet_expansion(arch):
+    """Output channels of a residual block per unit of its width: 4 for timm's Bottleneck, 1 for BasicBlock."""
+    return 4 if RESNET_CFG[arch][2] == "bottleneck" else 1
+
+
+def is_resnet_lib(arch):
+    """resnet34 / resnet50: the ResNets that run on libeffocr_resnet.so (16-bit convolutions); resnet18 runs on libeffocr_hip.so."""
+    return arch in RESNET_CFG and arch != "resnet18"
 
 
 def is_convnext(arch):
@@ -212,7 +228,8 @@ def param_shapes(arch, img_size=224, num_classes=0):
         s["norm.bias"] = (D,)
         return s
     if arch in RESNET_CFG:
-        depths, widths = RESNET_CFG[arch]
+        depths, widths, block = RESNET_CFG[arch]
+        exp = resnet_expansion(arch)
 
         def bn(p, c):
             s[p + ".weight"] = (c,)
@@ -226,14 +243,23 @@ def param_shapes(arch, img_size=224, num_classes=0):
         for li, (nb, w) in enumerate(zip(depths, widths), start=1):
             for bi in range(nb):
                 p = f"layer{li}.{bi}."
-                s[p + "conv1.weight"] = (w, cin, 3, 3)
-                bn(p + "bn1", w)
-                s[p + "conv2.weight"] = (w, w, 3, 3)
-                bn(p + "bn2", w)
-                if bi == 0 and li > 1:
-                    s[p + "downsample.0.weight"] = (w, cin, 1, 1)
-                    bn(p + "downsample.1", w)
-                cin = w
+                stride = 2 if (bi == 0 and li > 1) else 1
+                if block == "bottleneck":
+                    s[p + "conv1.weight"] = (w, cin, 1, 1)
+                    bn(p + "bn1", w)
+                    s[p + "conv2.weight"] = (w, w, 3, 3)
+                    bn(p + "bn2", w)
+                    s[p + "conv3.weight"] = (w * exp, w, 1, 1)
+                    bn(p + "bn3", w * exp)
+                else:
+                    s[p + "conv1.weight"] = (w, cin, 3, 3)
+                    bn(p + "bn1", w)
+                    s[p + "conv2.weight"] = (w, w, 3, 3)
+                    bn(p + "bn2", w)
+                if bi == 0 and (stride != 1 or cin != w * exp):
+                    s[p + "downsample.0.weight"] = (w * exp, cin, 1, 1)
+                    bn(p + "downsample.1", w * exp)
+                cin = w * exp
         return s
     if arch in CONVNEXT_CFG:
         depths, widths = CONVNEXT_CFG[arch]
@@ -382,6 +408,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_mobilenetv3(arch, seed, img_size, scale)
     if arch in SWIN_CFG:
         return _init_swin(arch, seed, img_size, scale)
+    if is_resnet_lib(arch):
+        return _init_resnet(arch, seed, img_size, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -535,6 +563,40 @@ def _init_swin(arch, seed, img_size, scale):
     return sd
 
 
+def _init_resnet(arch, seed, img_size, scale):
+    """resnet34 / resnet50 from a CPU Philox generator of their own (resnet18 keeps the generic stream of init_state_dict).
+    Convolutions are kaiming-normal (std sqrt(2 / fan_in)), as timm's.  scale="timm": BN at identity, with the last BN of every residual
+    branch at gamma 0 (timm's zero_init_last).  scale="unit": BN running means N(0, 0.1), running variances U(0.5, 1.5), betas N(0, 0.1),
+    gammas U(0.5, 1.5) except the last BN of a branch, U(0.2, 0.5) — so that the 16 residual additions keep the stream within a few
+    units, as a trained network's does, instead of doubling its variance per block."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x7265736E) % (1 << 63))
+    last = "bn3" if RESNET_CFG[arch][2] == "bottleneck" else "bn2"
+    sd = OrderedDict()
+    for k, shp in param_shapes(arch, img_size).items():
+        leaf = k.rsplit(".", 1)[-1]
+        bn = k.rsplit(".", 1)[0].rsplit(".", 1)[-1]
+        if len(shp) == 4:
+            v = torch.randn(shp, generator=g, dtype=torch.float32) * math.sqrt(2.0 / (shp[1] * shp[2] * shp[3]))
+        elif scale == "timm":
+            if leaf in ("bias", "running_mean"):
+                v = torch.zeros(shp)
+            elif leaf == "running_var":
+                v = torch.ones(shp)
+            else:
+                v = torch.zeros(shp) if bn == last else torch.ones(shp)
+        elif leaf == "running_var":
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+        elif leaf in ("bias", "running_mean"):
+            v = torch.randn(shp, generator=g, dtype=torch.float32) * 0.1
+        elif bn == last:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) * 0.3 + 0.2
+        else:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+        sd[k] = v.contiguous()
+    return sd
+
+
 def init_head(arch, num_classes, seed=0, scale="unit"):
     """Seeded classifier head from a CPU Philox generator of its own (seeded from ``seed`` and the tag 0x68656164): scale="unit"
     gives weights N(0, 1/D) and biases N(0, 0.1), so logits are O(1) for O(1) embeddings; scale="timm" gives timm's
@@ -621,8 +683,15 @@ def save_checkpoint(sd, path, prefix="net."):
 def infer_arch(sd):
     """Guess the architecture of a checkpoint from its parameter shapes."""
     sd = strip_prefix(sd)
-    if "conv1.weight" in sd and "layer4.1.conv2.weight" in sd:
-        return "resnet18"
+    if "conv1.weight" in sd and "layer4.0.conv1.weight" in sd:
+        # every ResNet has conv1 and layer4: the depth of layer3 and conv3 (Bottleneck) tell them apart
+        depths = tuple(1 + max((int(k.split(".")[1]) for k in sd if k.startswith(f"layer{i}.")), default=-1) for i in range(1, 5))
+        block = "bottleneck" if "layer1.0.conv3.weight" in sd else "basic"
+        for name, (dep, _, blk) in RESNET_CFG.items():
+            if dep == depths and blk == block:
+                return name
+        raise ValueError(f"unsupported ResNet: {block} blocks, depths {depths} (supported: "
+                         + ", ".join(f"{n} {c[2]} {c[0]}" for n, c in RESNET_CFG.items()) + ")")
     if "pos_embed" in sd:
         D = sd["pos_embed"].shape[-1]
         depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
