@@ -1,0 +1,146 @@
+// C ABI of libeffocr_convops.so — a TEST-ONLY library (DESIGN.md "Operator parity (convolutions and pools)").  Thin wrappers over the
+// convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, which this library compiles once more with
+// hidden visibility, so that tests/test_gpu_convops.py compares each kernel on its own with a float64 reference.  No product library
+// exports these and no product code loads this one: libeffocr_hip.so is at its size cap (DESIGN.md "Library split").
+// All device pointers are caller-owned, `stream` is a hipStream_t (NULL = the default stream); every call returns 0 or a negative
+// EFFOCR_E* code (include/effocr_hip.h) whose message effocr_convops_last_error() holds for the calling thread.
+#include "../../include/effocr_hip.h"
+#include "common.hpp"
+#include "kernels.hpp"
+#include "resnet16.hpp"
+
+#include <string>
+
+#define CONVOPS_API extern "C" __attribute__((visibility("default")))
+#define EFFOCR_CONVOPS_ABI_VERSION 1
+
+namespace effocr {
+
+// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
+static thread_local std::string g_convops_err;
+void set_error(const std::string& msg) { g_convops_err = msg; }
+int fail(int code, const std::string& msg) { g_convops_err = msg; return code; }
+int check_launch(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return EFFOCR_OK;
+}
+int device_cus() {
+  static int cache[64] = {0};                            // benign race: every thread computes the same value
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cache[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    cache[dev] = v;
+  }
+  return cache[dev];
+}
+
+extern thread_local int convops_last_nw, convops_last_ksplit;   // resnet.hip under -DEFFOCR_CONVOPS
+
+}  // namespace effocr
+
+using namespace effocr;
+
+CONVOPS_API int effocr_convops_abi_version(void) { return EFFOCR_CONVOPS_ABI_VERSION; }
+CONVOPS_API const char* effocr_convops_last_error(void) { return g_convops_err.c_str(); }
+CONVOPS_API int effocr_convops_device_cus(void) { return device_cus(); }
+// channel tile (32 / 64 / 128) and K split of the calling thread's last effocr_convops_conv2d launch (0, 0 before the first)
+CONVOPS_API void effocr_convops_last_dispatch(int* nw, int* ksplit) {
+  if (nw) *nw = convops_last_nw;
+  if (ksplit) *ksplit = convops_last_ksplit;
+}
+
+// resnet.hip conv2d_nhwc: every field of ConvArgs (kernels.hpp) but ksplit, which the dispatcher sets
+CONVOPS_API int effocr_convops_conv2d(const float* in, const float* w, const float* bias, const float* resid, float* out, int B, int H, int W, int Cin,
+                                      int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int relu, int in_ld, int in_off, int out_ld,
+                                      int out_off, int res_ld, int res_off, int silu, float* partial, size_t partial_bytes, const void* w16,
+                                      void* stream) {
+  convops_last_nw = 0; convops_last_ksplit = 0;
+  if (!in || !bias || !out || (!w && !w16)) return fail(EFFOCR_EINVAL, "convops_conv2d: NULL argument");
+  if (B < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || OH < 0 || OW < 0 || (in_ld | in_off | out_ld | out_off | res_ld | res_off) < 0)
+    return fail(EFFOCR_EINVAL, "convops_conv2d: bad shape");
+  if (relu && silu) return fail(EFFOCR_EINVAL, "convops_conv2d: relu and silu are exclusive");
+  if (OH > 0 && ((OH - 1) * stride - pad >= H || (OH - 1) * stride - pad + KH < 1)) return fail(EFFOCR_EINVAL, "convops_conv2d: OH outside the input");
+  if (OW > 0 && ((OW - 1) * stride - pad >= W || (OW - 1) * stride - pad + KW < 1)) return fail(EFFOCR_EINVAL, "convops_conv2d: OW outside the input");
+  if ((in_ld && in_off + Cin > in_ld) || (out_ld && out_off + Cout > out_ld) || (res_ld && res_off + Cout > res_ld) || (!in_ld && in_off) ||
+      (!out_ld && out_off) || (!res_ld && res_off))
+    return fail(EFFOCR_EINVAL, "convops_conv2d: a channel slice outside its row");
+  ConvArgs a{};
+  a.in = in; a.w = w; a.bias = bias; a.resid = resid; a.out = out;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.OH = OH; a.OW = OW; a.relu = relu;
+  a.in_ld = in_ld; a.in_off = in_off; a.out_ld = out_ld; a.out_off = out_off; a.res_ld = res_ld; a.res_off = res_off;
+  a.silu = silu; a.partial = partial; a.partial_bytes = partial ? partial_bytes : 0; a.ksplit = 0; a.w16 = w16;
+  return conv2d_nhwc(a, static_cast<hipStream_t>(stream));
+}
+
+// resnet16.hip rn_conv16: Conv16Args + prec (0 = bf16, 1 = f16)
+CONVOPS_API int effocr_convops_conv16(int prec, const void* in, const void* w, const float* bias, const void* resid, void* out, int B, int H, int W,
+                                      int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int relu, void* stream) {
+  if (prec != PREC_BF16 && prec != PREC_FP16) return fail(EFFOCR_EINVAL, "convops_conv16: prec must be bf16 (0) or f16 (1)");
+  if (!in || !w || !bias || !out) return fail(EFFOCR_EINVAL, "convops_conv16: NULL argument");
+  if (B < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || OH < 0 || OW < 0) return fail(EFFOCR_EINVAL, "convops_conv16: bad shape");
+  if (OH > 0 && ((OH - 1) * stride - pad >= H || (OH - 1) * stride - pad + KH < 1)) return fail(EFFOCR_EINVAL, "convops_conv16: OH outside the input");
+  if (OW > 0 && ((OW - 1) * stride - pad >= W || (OW - 1) * stride - pad + KW < 1)) return fail(EFFOCR_EINVAL, "convops_conv16: OW outside the input");
+  Conv16Args a{};
+  a.in = in; a.w = w; a.bias = bias; a.resid = resid; a.out = out;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.OH = OH; a.OW = OW; a.relu = relu;
+  return rn_conv16(prec, a, static_cast<hipStream_t>(stream));
+}
+
+CONVOPS_API int effocr_convops_im2col_conv1(const float* x, float* col, int B, int H, int W, int OH, int OW, void* stream) {
+  if (!x || !col) return fail(EFFOCR_EINVAL, "convops_im2col_conv1: NULL argument");
+  return im2col_conv1(x, col, B, H, W, OH, OW, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_im2col_nchw(const float* x, float* col, int B, int Cin, int H, int W, int KH, int KW, int stride, int pad, int OH, int OW,
+                                           int kpad, void* stream) {
+  if (!x || !col) return fail(EFFOCR_EINVAL, "convops_im2col_nchw: NULL argument");
+  return im2col_nchw(x, col, B, Cin, H, W, KH, KW, stride, pad, OH, OW, kpad, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, int OH, int OW, void* stream) {
+  if (!in || !out) return fail(EFFOCR_EINVAL, "convops_maxpool3x3s2: NULL argument");
+  if (C < 4 || C % 4) return fail(EFFOCR_EUNSUPPORTED, "convops_maxpool3x3s2: C must be a multiple of 4");
+  return maxpool3x3s2_nhwc(in, out, B, H, W, C, OH, OW, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_avgpool(const float* in, float* out, int B, int HW, int C, int l2norm, void* stream) {
+  if (!in || !out) return fail(EFFOCR_EINVAL, "convops_avgpool: NULL argument");
+  return global_avgpool_nhwc(in, out, B, HW, C, l2norm, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_stem6x6s2(const float* x, const float* w, int w_ld, const float* wt, const float* bias, float* out, int B, int H, int W,
+                                         int OH, int OW, int out_ld, int out_off, int silu, void* stream) {
+  if (!x || !w || !bias || !out) return fail(EFFOCR_EINVAL, "convops_stem6x6s2: NULL argument");
+  return stem6x6s2_nchw(x, w, w_ld, wt, bias, out, B, H, W, OH, OW, out_ld, out_off, silu, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_stem6x6s2_g16(const float* x, const float* wt, int wt_ld, const float* bias, float* out, int B, int H, int W, int OH,
+                                             int OW, int out_ld, int out_off, int cout, int cout_st, void* stream) {
+  if (!x || !wt || !bias || !out) return fail(EFFOCR_EINVAL, "convops_stem6x6s2_g16: NULL argument");
+  return stem6x6s2_g16_nchw(x, wt, wt_ld, bias, out, B, H, W, OH, OW, out_ld, out_off, cout, cout_st, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_upsample2x(const float* in, int in_ld, int in_off, float* out, int out_ld, int out_off, int B, int H, int W, int C,
+                                          void* stream) {
+  if (!in || !out) return fail(EFFOCR_EINVAL, "convops_upsample2x: NULL argument");
+  return upsample2x_nhwc(in, in_ld, in_off, out, out_ld, out_off, B, H, W, C, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_maxpool5(const float* in, int in_ld, int in_off, float* out, int out_ld, int out_off, int B, int H, int W, int C,
+                                        void* stream) {
+  if (!in || !out) return fail(EFFOCR_EINVAL, "convops_maxpool5: NULL argument");
+  return maxpool5_nhwc(in, in_ld, in_off, out, out_ld, out_off, B, H, W, C, static_cast<hipStream_t>(stream));
+}
+
+CONVOPS_API int effocr_convops_im2col16(int prec, const float* x, void* col, int B, int H, int W, int OH, int OW, void* stream) {
+  if (prec != PREC_BF16 && prec != PREC_FP16) return fail(EFFOCR_EINVAL, "convops_im2col16: prec must be bf16 (0) or f16 (1)");
+  if (!x || !col) return fail(EFFOCR_EINVAL, "convops_im2col16: NULL argument");
+  return rn_im2col16(prec, x, col, B, H, W, OH, OW, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_maxpool16(int prec, const void* in, void* out, int B, int H, int W, int C, int OH, int OW, void* stream) {
+  if (prec != PREC_BF16 && prec != PREC_FP16) return fail(EFFOCR_EINVAL, "convops_maxpool16: prec must be bf16 (0) or f16 (1)");
+  if (!in || !out) return fail(EFFOCR_EINVAL, "convops_maxpool16: NULL argument");
+  return rn_maxpool16(prec, in, out, B, H, W, C, OH, OW, static_cast<hipStream_t>(stream));
+}
+// prec: the element type of `in` (0 = bf16, 1 = f16, 2 = fp32); status: optional device int, ORed with 1 on a non-finite embedding
+CONVOPS_API int effocr_convops_avgpool16(int prec, const void* in, float* emb, int B, int HW, int C, int l2norm, int* status, void* stream) {
+  if (prec < 0 || prec > 2) return fail(EFFOCR_EINVAL, "convops_avgpool16: unknown element type");
+  if (!in || !emb) return fail(EFFOCR_EINVAL, "convops_avgpool16: NULL argument");
+  return rn_avgpool(prec, in, emb, B, HW, C, l2norm, status, static_cast<hipStream_t>(stream));
+}

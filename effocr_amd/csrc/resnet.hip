@@ -322,9 +322,9 @@ __global__ __launch_bounds__(256, (NW == 32 ? 3 : 2)) void conv_igemm_kernel(Con
     f32x4 v = *reinterpret_cast<const f32x4*>(tile + p * TS + c4 * 4);
     const bool ok = m < M && n < a.Cout;
     if (a.resid && ok) v += *reinterpret_cast<const f32x4*>(a.resid + (int64_t)m * a.res_ld + a.res_off + n);
-    if (a.relu) {
+    if (a.relu) {                                            // NaN-propagating, as torch's relu (fmaxf returns the 0): v_maximum3_f32
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
     }
     if (ok) *reinterpret_cast<f32x4*>(a.out + (int64_t)m * a.out_ld + a.out_off + n) = v;
   }
@@ -346,9 +346,9 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(ConvArgs a, int64_t M)
     for (int e = 0; e < 4; ++e) v[e] = silu_fast(v[e]);
   }
   if (a.resid) v += *reinterpret_cast<const f32x4*>(a.resid + m * a.res_ld + a.res_off + n);
-  if (a.relu) {
+  if (a.relu) {                                              // NaN-propagating, as in conv_igemm_kernel
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+    for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
   }
   *reinterpret_cast<f32x4*>(a.out + m * a.out_ld + a.out_off + n) = v;
 }
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void im2col_conv1_kernel(const float* __restri
   col[id] = v;
 }
 
-// max_pool2d(kernel 3, stride 2, padding 1) on NHWC (padding never wins: -inf)
+// max_pool2d(kernel 3, stride 2, padding 1) on NHWC (padding never wins: -inf; a NaN wins, as in torch)
 __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                       int B, int H, int W, int C, int OH, int OW) {
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ 
       if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(in + ((b * H + iy) * W + ix) * C + c4 * 4);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
+        for (int e = 0; e < 4; ++e) m[e] = __builtin_elementwise_maximum(m[e], v[e]);   // IEEE 754-2019 maximum: a NaN wins
       }
     }
   *reinterpret_cast<f32x4*>(out + p * C + c4 * 4) = m;
@@ -421,7 +421,8 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const float* __restrict__ 
     for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
     if ((tid & 63) == 0) red[tid >> 6] = ss;
     __syncthreads();
-    const float nrm = fmaxf(sqrtf(red[0] + red[1] + red[2] + red[3]), 1e-12f);
+    const float nr = sqrtf(red[0] + red[1] + red[2] + red[3]);
+    const float nrm = nr < 1e-12f ? 1e-12f : nr;             // F.normalize's clamp; a NaN norm stays NaN, as torch's clamp_min
     v[0] = v[0] / nrm; v[1] = v[1] / nrm;
   }
 #pragma unroll
@@ -432,6 +433,12 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const float* __restrict__ 
 }
 
 }  // namespace
+
+#ifdef EFFOCR_CONVOPS
+// libeffocr_convops.so only (the test-only operator library): the channel tile and K split of the calling thread's last conv2d_nhwc
+// launch, host side, so that an operator test asserts the kernel variant it meant to run; the product libraries never define the macro
+thread_local int convops_last_nw = 0, convops_last_ksplit = 0;
+#endif
 
 int conv2d_nhwc(const ConvArgs& a_in, hipStream_t s) {
   ConvArgs a = a_in;
@@ -471,6 +478,9 @@ int conv2d_nhwc(const ConvArgs& a_in, hipStream_t s) {
     while (sp > 1 && (size_t)sp * M * a.Cout * 4 > a.partial_bytes) --sp;
     a.ksplit = (int)sp;
   }
+#ifdef EFFOCR_CONVOPS
+  convops_last_nw = nw; convops_last_ksplit = a.ksplit;
+#endif
   const dim3 g((unsigned)grid, (unsigned)a.ksplit);
   if (a.w16) {
     if (nw == 32) hipLaunchKernelGGL((conv_igemm_kernel<__bf16, 32>), g, dim3(256), 0, s, a);

@@ -254,7 +254,8 @@ __global__ __launch_bounds__(256) void rn_avgpool_kernel(const T* __restrict__ i
     for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
     if ((tid & 63) == 0) red[tid >> 6] = ss;
     __syncthreads();
-    const float nrm = fmaxf(sqrtf(red[0] + red[1] + red[2] + red[3]), 1e-12f);
+    const float nr = sqrtf(red[0] + red[1] + red[2] + red[3]);
+    const float nrm = nr < 1e-12f ? 1e-12f : nr;             // F.normalize's clamp; a NaN norm stays NaN, as torch's clamp_min
 #pragma unroll
     for (int t = 0; t < 8; ++t) v[t] = v[t] / nrm;
   }

@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void maxpool5_kernel(const float* __restrict__
       if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(in + ((b * H + iy) * W + ix) * in_ld + in_off + c4 * 4);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
+        for (int e = 0; e < 4; ++e) m[e] = __builtin_elementwise_maximum(m[e], v[e]);   // IEEE 754-2019 maximum: a NaN wins, as in torch's max_pool2d
       }
     }
   *reinterpret_cast<f32x4*>(out + p * out_ld + out_off + c4 * 4) = m;

@@ -1,0 +1,69 @@
+"""ctypes binding of effocr_amd/libeffocr_convops.so, the TEST-ONLY operator library (csrc/convops_api.hip): thin wrappers over the
+convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip.  `make` builds it next to the product
+libraries (``__graft_entry__.build()``); a missing library is an error here — no skip, no fallback."""
+
+import ctypes
+import os
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SO_PATH = os.path.join(ROOT, "effocr_amd", "libeffocr_convops.so")
+ABI_VERSION = 1
+PREC_BF16, PREC_FP16, PREC_FP32 = 0, 1, 2
+OK, EINVAL, EUNSUPPORTED = 0, -1, -2
+
+_c = ctypes
+_vp, _i, _sz = _c.c_void_p, _c.c_int, _c.c_size_t
+SIGNATURES = {
+    "effocr_convops_abi_version": (_i, []),
+    "effocr_convops_last_error": (_c.c_char_p, []),
+    "effocr_convops_device_cus": (_i, []),
+    "effocr_convops_last_dispatch": (None, [_c.POINTER(_i), _c.POINTER(_i)]),
+    # in, w, bias, resid, out, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, relu, in_ld, in_off, out_ld, out_off, res_ld, res_off, silu,
+    # partial, partial_bytes, w16, stream
+    "effocr_convops_conv2d": (_i, [_vp] * 5 + [_i] * 19 + [_vp, _sz, _vp, _vp]),
+    # prec, in, w, bias, resid, out, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, relu, stream
+    "effocr_convops_conv16": (_i, [_i] + [_vp] * 5 + [_i] * 12 + [_vp]),
+    "effocr_convops_im2col_conv1": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),                    # x, col, B, H, W, OH, OW
+    "effocr_convops_im2col_nchw": (_i, [_vp, _vp] + [_i] * 11 + [_vp]),                    # x, col, B, Cin, H, W, KH, KW, stride, pad, OH, OW, kpad
+    "effocr_convops_maxpool3x3s2": (_i, [_vp, _vp] + [_i] * 6 + [_vp]),                    # in, out, B, H, W, C, OH, OW
+    "effocr_convops_avgpool": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),                         # in, out, B, HW, C, l2norm
+    "effocr_convops_stem6x6s2": (_i, [_vp, _vp, _i, _vp, _vp, _vp] + [_i] * 8 + [_vp]),    # x, w, w_ld, wt, bias, out, B, H, W, OH, OW, out_ld, out_off, silu
+    "effocr_convops_stem6x6s2_g16": (_i, [_vp, _vp, _i, _vp, _vp] + [_i] * 9 + [_vp]),     # x, wt, wt_ld, bias, out, B, H, W, OH, OW, out_ld, out_off, cout, cout_st
+    "effocr_convops_upsample2x": (_i, [_vp, _i, _i, _vp, _i, _i] + [_i] * 4 + [_vp]),      # in, in_ld, in_off, out, out_ld, out_off, B, H, W, C
+    "effocr_convops_maxpool5": (_i, [_vp, _i, _i, _vp, _i, _i] + [_i] * 4 + [_vp]),
+    "effocr_convops_im2col16": (_i, [_i, _vp, _vp] + [_i] * 5 + [_vp]),                    # prec, x, col, B, H, W, OH, OW
+    "effocr_convops_maxpool16": (_i, [_i, _vp, _vp] + [_i] * 6 + [_vp]),                   # prec, in, out, B, H, W, C, OH, OW
+    "effocr_convops_avgpool16": (_i, [_i, _vp, _vp] + [_i] * 4 + [_vp, _vp]),              # prec, in, emb, B, HW, C, l2norm, status
+}
+EXPORTS = sorted(SIGNATURES)
+
+_lib = None
+
+
+def lib():
+    """The loaded library with every wrapper declared; raises when the library or one of its symbols is missing."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO_PATH):
+            raise RuntimeError(f"{SO_PATH} is missing: build it with python -c 'import __graft_entry__ as g; g.build()'")
+        L = ctypes.CDLL(SO_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)                              # AttributeError: a wrapper that is not exported
+            fn.restype, fn.argtypes = res, args
+        _lib = L
+    return _lib
+
+
+def last_error():
+    return lib().effocr_convops_last_error().decode()
+
+
+def last_dispatch():
+    """(channel tile, K split) of this thread's last effocr_convops_conv2d launch."""
+    nw, ks = _i(0), _i(0)
+    lib().effocr_convops_last_dispatch(ctypes.byref(nw), ctypes.byref(ks))
+    return nw.value, ks.value
+
+
+def ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())

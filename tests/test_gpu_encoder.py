@@ -474,6 +474,23 @@ def test_stream_split_vit_base(dev):
     enc.check_status()
 
 
+def test_resnet18_nan_crop_gives_a_nonfinite_embedding(dev):
+    """A NaN pixel reaches the embedding of its crop, as in the CPU restatement (torch's relu and max_pool2d propagate NaN), and leaves
+    the other crops of the call bit for bit as they were."""
+    from effocr_amd.encoders import HipEncoder
+    sd = init_state_dict("resnet18", seed=3, img_size=64)
+    enc = HipEncoder("resnet18", sd, img_size=64, precision="fp32", device=dev)
+    x = torch.randn(4, 3, 64, 64, generator=torch.Generator().manual_seed(9))
+    clean = enc.forward(x.to(dev)).cpu()
+    assert torch.isfinite(clean).all()
+    x[2, 1, 20, 21] = float("nan")
+    ref = encoder_forward("resnet18", sd, x)
+    got = enc.forward(x.to(dev)).cpu()
+    assert not torch.isfinite(ref[2]).any() and torch.isfinite(ref[[0, 1, 3]]).all()
+    assert torch.equal(torch.isnan(got), torch.isnan(ref))
+    assert torch.equal(got[[0, 1, 3]], clean[[0, 1, 3]])
+
+
 def test_resnet_and_localizer_do_not_depend_on_the_call_size(dev):
     """resnet18 (split-K convolutions for launches of few tiles) and the YOLOv5s localizer at 1 vs 16 images per call: exact-fp32
     MFMA operands either way, only the order of the split partial sums moves: <= 2e-6 relative."""

@@ -132,19 +132,22 @@ def test_l2_normalize_fused(dev, prec):
     enc.check_status()
 
 
-@pytest.mark.parametrize("prec", ["fp16", "bf16"])
+@pytest.mark.parametrize("prec", ["fp32", "fp16", "bf16"])
 def test_status_reports_nonfinite_input(dev, prec):
+    """Every precision, a NaN and an inf crop: the fp32 mode's ReLU and max pool propagate a NaN as the 16-bit path's do
+    (tests/test_gpu_convops.py)."""
     enc = _engine("resnet34", W.init_state_dict("resnet34", seed=5), prec, dev)
-    x = _crops(4, 8).to(dev)
-    enc.forward(x)
-    enc.check_status()
-    x[2, 1, 10, 10] = float("nan")
-    emb = enc.forward(x)
-    with pytest.raises(_lib.EffOCRHipError, match="code -6"):
+    for bad in (float("nan"), float("inf")):
+        x = _crops(4, 8).to(dev)
+        enc.forward(x)
         enc.check_status()
-    assert not torch.isfinite(emb[2]).all()
-    assert torch.isfinite(emb[[0, 1, 3]]).all()            # the other crops of the call are untouched
-    enc.check_status()                                     # read-and-clear
+        x[2, 1, 10, 10] = bad
+        emb = enc.forward(x)
+        with pytest.raises(_lib.EffOCRHipError, match="code -6"):
+            enc.check_status()
+        assert not torch.isfinite(emb[2]).all()
+        assert torch.isfinite(emb[[0, 1, 3]]).all()        # the other crops of the call are untouched
+        enc.check_status()                                 # read-and-clear
 
 
 def test_workspace_too_small_is_refused(dev):
