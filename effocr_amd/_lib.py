@@ -296,6 +296,46 @@ def resnet_lib():
     return _resnet
 
 
+# libeffocr_mnv3.so (include/effocr_mnv3.h): the MobileNetV3 small_075 / small_100 / large_100 encoders, a library of its own for the same
+# reason (a forward of its own, activations in HBM between blocks).  Bound by mnv3_lib(); its functions are not part of EXPORTS either.
+MNV3_SO_PATH = os.path.join(_HERE, "libeffocr_mnv3.so")
+MNV3_ABI_VERSION = 1     # == EFFOCR_MNV3_ABI_VERSION of include/effocr_mnv3.h
+_mnv3 = None
+
+
+def _mnv3_signatures():
+    return {k.replace("effocr_swin_", "effocr_mnv3_"): v for k, v in _swin_signatures().items()}
+
+
+MNV3_EXPORTS = tuple(sorted(_mnv3_signatures()))
+
+
+def mnv3_lib():
+    """Load (once) and return the ctypes handle of libeffocr_mnv3.so; raises if it is missing or its ABI version differs."""
+    global _mnv3
+    with _lock:
+        if _mnv3 is None:
+            if not os.path.exists(MNV3_SO_PATH):
+                raise EffOCRHipError(f"{MNV3_SO_PATH} not found: the MobileNetV3 encoder library is required (no CPU fallback). "
+                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
+            handle = ctypes.CDLL(MNV3_SO_PATH)
+            for name, (res, args) in _mnv3_signatures().items():
+                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
+                fn.restype, fn.argtypes = res, args
+            got = handle.effocr_mnv3_abi_version()
+            if got != MNV3_ABI_VERSION:
+                raise EffOCRHipError(f"libeffocr_mnv3.so ABI version {got} != {MNV3_ABI_VERSION} expected by this package: rebuild "
+                                     "(make -C effocr_amd/csrc)")
+            _mnv3 = handle
+    return _mnv3
+
+
+def mnv3_check(rc, what=""):
+    if rc != 0:
+        msg = mnv3_lib().effocr_mnv3_last_error()
+        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
 def resnet_check(rc, what=""):
     if rc != 0:
         msg = resnet_lib().effocr_resnet_last_error()

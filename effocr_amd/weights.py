@@ -14,7 +14,7 @@ project, so those names could not be checked against timm itself here; the archi
 shapes are pinned against ``transformers.ConvNextModel`` by the tests (tests/test_convnext_host.py), the same
 caveat that applies to the faiss index layout of knn.py.
 
-MobileNetV3 (``mobilenetv3_small_050``) is described by timm's arch-def strings and a channel multiplier
+MobileNetV3 (``mobilenetv3_small_050`` / ``_075`` / ``_100``, ``mobilenetv3_large_100``) is described by timm's arch-def strings and a channel multiplier
 (``mobilenetv3_blocks``), from which the key names and shapes follow (``conv_stem``, ``bn1``,
 ``blocks.i.j.{conv_pw,bn1,conv_dw,bn2,se.conv_reduce,se.conv_expand,conv_pwl,bn3}``, ``conv_head``); the
 builder is pinned by the parameter counts of three widths (tests/test_mobilenetv3_host.py).
@@ -50,10 +50,12 @@ CONVNEXT_CFG = {
     "convnext_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
 }
 MOBILENETV3_CFG = {
-    # name: channel multiplier — timm mobilenetv3.py _gen_mobilenet_v3 ("small"); only _050 has kernels, the other two widths pin the builder
+    # name: channel multiplier — timm mobilenetv3.py _gen_mobilenet_v3; _050 runs on libeffocr_hip.so (LDS-resident kernels), the other
+    # three on libeffocr_mnv3.so (is_mnv3_lib)
     "mobilenetv3_small_050": 0.5,
     "mobilenetv3_small_075": 0.75,
     "mobilenetv3_small_100": 1.0,
+    "mobilenetv3_large_100": 1.0,
 }
 MOBILENETV3_ARCH_DEF = (
     # timm's arch-def strings for MobileNetV3-Small: one list per stage; "nre" = ReLU, otherwise hard-swish
@@ -64,11 +66,22 @@ MOBILENETV3_ARCH_DEF = (
     ("ir_r3_k5_s2_e6_c96_se0.25",),
     ("cn_r1_k1_s1_c576",),
 )
+MOBILENETV3_LARGE_ARCH_DEF = (
+    # timm's arch-def strings for MobileNetV3-Large (_gen_mobilenet_v3, the non-small branch)
+    ("ds_r1_k3_s1_e1_c16_nre",),
+    ("ir_r1_k3_s2_e4_c24_nre", "ir_r1_k3_s1_e3_c24_nre"),
+    ("ir_r3_k5_s2_e3_c40_se0.25_nre",),
+    ("ir_r1_k3_s2_e6_c80", "ir_r1_k3_s1_e2.5_c80", "ir_r2_k3_s1_e2.3_c80"),
+    ("ir_r2_k3_s1_e6_c112_se0.25",),
+    ("ir_r3_k5_s2_e6_c160_se0.25",),
+    ("cn_r1_k1_s1_c960",),
+)
 SWIN_CFG = {
     # name: (embed_dim, depths, heads, window) — timm swin_transformer.py; head dim 32 in every stage, mlp ratio 4, patch 4
     "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24), 7),
 }
-MOBILENETV3_FEATURES = 1024           # conv_head width (not scaled by the multiplier)
+MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
+MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
 PATCH = 16
 
 
@@ -82,13 +95,14 @@ def make_divisible(v, divisor=8, min_value=None, round_limit=0.9):
 
 
 def mobilenetv3_blocks(arch):
-    """(stem channels, [block dicts], head width) of a MobileNetV3-Small width, built from MOBILENETV3_ARCH_DEF the way timm's
-    _efficientnet_builder does.  A block dict has: key (e.g. "blocks.2.1"), type ("ds" | "ir" | "cn"), cin, mid, cout, k, stride,
+    """(stem channels, [block dicts], head width) of a MobileNetV3 (Small or Large, chosen by name), built from MOBILENETV3_ARCH_DEF /
+    MOBILENETV3_LARGE_ARCH_DEF the way timm's _efficientnet_builder does.  A block dict has: key (e.g. "blocks.2.1"), type ("ds" | "ir" | "cn"), cin, mid, cout, k, stride,
     se (SE width, 0 = none), hs (hard-swish, else ReLU), res (residual)."""
     mult = MOBILENETV3_CFG[arch]
+    large = is_mobilenetv3_large(arch)
     stem = 16 if mult < 0.75 else make_divisible(16 * mult)   # fix_stem = multiplier < 0.75
     blocks, cin = [], stem
-    for si, stage in enumerate(MOBILENETV3_ARCH_DEF):
+    for si, stage in enumerate(MOBILENETV3_LARGE_ARCH_DEF if large else MOBILENETV3_ARCH_DEF):
         bi = 0
         for bs in stage:
             ops = bs.split("_")
@@ -111,11 +125,21 @@ def mobilenetv3_blocks(arch):
                                    hs="nre" not in opt, res=(ops[0] != "cn" and stride == 1 and cin == cout)))
                 cin = cout
                 bi += 1
-    return stem, blocks, MOBILENETV3_FEATURES
+    return stem, blocks, MOBILENETV3_LARGE_FEATURES if large else MOBILENETV3_FEATURES
 
 
 def is_mobilenetv3(arch):
     return arch in MOBILENETV3_CFG
+
+
+def is_mobilenetv3_large(arch):
+    return arch in MOBILENETV3_CFG and arch.startswith("mobilenetv3_large_")
+
+
+def is_mnv3_lib(arch):
+    """The MobileNetV3s that run on libeffocr_mnv3.so (activations in HBM between blocks): every one but mobilenetv3_small_050, which
+    keeps its LDS-resident kernels in libeffocr_hip.so."""
+    return arch in MOBILENETV3_CFG and arch != "mobilenetv3_small_050"
 
 
 def is_vit(arch):
@@ -130,7 +154,7 @@ def embed_dim(arch):
     if arch in CONVNEXT_CFG:
         return CONVNEXT_CFG[arch][1][-1]
     if arch in MOBILENETV3_CFG:
-        return MOBILENETV3_FEATURES
+        return MOBILENETV3_LARGE_FEATURES if is_mobilenetv3_large(arch) else MOBILENETV3_FEATURES
     if arch in SWIN_CFG:
         return SWIN_CFG[arch][0] * 8
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
@@ -712,7 +736,11 @@ def infer_arch(sd):
             if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
                 return name
     if "conv_stem.weight" in sd and "conv_head.weight" in sd:
+        # Large has a seventh stage (blocks.6.0, the 960-wide ConvBnAct), Small ends at blocks.5.0; the width follows from the shapes
+        large = "blocks.6.0.conv.weight" in sd
         for name in MOBILENETV3_CFG:
+            if is_mobilenetv3_large(name) != large:
+                continue
             want = param_shapes(name)
             if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
                 return name
