@@ -330,6 +330,55 @@ def mnv3_lib():
     return _mnv3
 
 
+# libeffocr_effnet.so (include/effocr_effnet.h): the EfficientNet-B0 encoders efficientnet_b0 / tf_efficientnet_b0, a library of its own for
+# the same reason (its own stem, depthwise and squeeze-excite kernels, plus a hidden copy of libeffocr_mnv3.so's pointwise GEMM).  Bound by
+# effnet_lib(); its functions are not part of EXPORTS either.
+EFFNET_SO_PATH = os.path.join(_HERE, "libeffocr_effnet.so")
+EFFNET_ABI_VERSION = 1     # == EFFOCR_EFFNET_ABI_VERSION of include/effocr_effnet.h
+_effnet = None
+
+
+def _effnet_signatures():
+    c = ctypes
+    vp, i32 = c.c_void_p, c.c_int
+    sig = {k.replace("effocr_swin_", "effocr_effnet_"): v for k, v in _swin_signatures().items()}
+    sig["effocr_effnet_forward"] = (i32, [vp, vp, i32, i32, vp, i32, vp, c.c_size_t, vp])      # (the crop type after the crops)
+    sig["effocr_effnet_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_effnet_op_tiles"] = (i32, [i32])                                                # test entry points
+    sig["effocr_effnet_op_stem"] = (i32, [vp, i32, i32, i32, vp, vp, vp, vp])
+    sig["effocr_effnet_op_dw_se"] = (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp])
+    return sig
+
+
+EFFNET_EXPORTS = tuple(sorted(_effnet_signatures()))
+
+
+def effnet_lib():
+    """Load (once) and return the ctypes handle of libeffocr_effnet.so; raises if it is missing or its ABI version differs."""
+    global _effnet
+    with _lock:
+        if _effnet is None:
+            if not os.path.exists(EFFNET_SO_PATH):
+                raise EffOCRHipError(f"{EFFNET_SO_PATH} not found: the EfficientNet encoder library is required (no CPU fallback). "
+                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
+            handle = ctypes.CDLL(EFFNET_SO_PATH)
+            for name, (res, args) in _effnet_signatures().items():
+                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
+                fn.restype, fn.argtypes = res, args
+            got = handle.effocr_effnet_abi_version()
+            if got != EFFNET_ABI_VERSION:
+                raise EffOCRHipError(f"libeffocr_effnet.so ABI version {got} != {EFFNET_ABI_VERSION} expected by this package: rebuild "
+                                     "(make -C effocr_amd/csrc)")
+            _effnet = handle
+    return _effnet
+
+
+def effnet_check(rc, what=""):
+    if rc != 0:
+        msg = effnet_lib().effocr_effnet_last_error()
+        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
 def mnv3_check(rc, what=""):
     if rc != 0:
         msg = mnv3_lib().effocr_mnv3_last_error()

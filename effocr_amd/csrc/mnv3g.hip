@@ -19,7 +19,7 @@ namespace effocr {
 namespace {
 
 __device__ __forceinline__ float mg_act(float x, int a) {
-  return a == MG_ACT_RELU ? fmaxf(x, 0.0f) : a == MG_ACT_HS ? x * (fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f) : x;
+  return a == MG_ACT_RELU ? fmaxf(x, 0.0f) : a == MG_ACT_HS ? x * (fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f) : a == MG_ACT_SILU ? silu_fast(x) : x;
 }
 __device__ __forceinline__ float mg_hsig(float x) { return fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
 

@@ -8,7 +8,7 @@
 
 namespace effocr {
 
-enum { MG_ACT_NONE = 0, MG_ACT_RELU = 1, MG_ACT_HS = 2 };
+enum { MG_ACT_NONE = 0, MG_ACT_RELU = 1, MG_ACT_HS = 2, MG_ACT_SILU = 3 };   // SILU: libeffocr_effnet.so's forward only
 constexpr int MG_STEM_C = 16;          // stem channels of every supported width (fixed 16 below 0.75, make_divisible(16 m) = 16 up to 1.0)
 
 // stem: x [B,3,S,S] fp32 NCHW -> out [B,S/2,S/2,16] = hard-swish(conv3x3/2 pad 1 (x; w [27][16] tap-major, BN folded) + b)

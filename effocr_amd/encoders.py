@@ -501,12 +501,100 @@ class MobileNetV3Encoder(HipEncoder):
         raise NotImplementedError("the MobileNetV3 family encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
 
 
+class EfficientNetEncoder(HipEncoder):
+    """HipEncoder's interface over libeffocr_effnet.so (include/effocr_effnet.h): efficientnet_b0 / tf_efficientnet_b0 at any img_size that
+    is a multiple of 32 from 32 to 224, fp32 crops in every precision mode (the stem is an fp32 conv).  The two names share keys and
+    shapes: ``arch`` alone selects the BN eps and the padding.  Same per-stream grow-only workspaces with their sticky status word; no
+    stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
+
+    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
+        if precision not in _lib.PREC:
+            raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
+        self.device = _lib.require_gpu(device)
+        self.arch, self.img_size, self.precision = arch, int(img_size), precision
+        self._L = _lib.effnet_lib()
+        self._lock = threading.Lock()
+        self._h = ctypes.c_void_p()
+        _lib.effnet_check(self._L.effocr_effnet_create(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)),
+                          "effocr_effnet_create")
+        self.embed_dim = int(self._L.effocr_effnet_embed_dim(self._h))
+        sd = W.strip_prefix(state_dict)
+        W.check_state_dict(arch, sd, self.img_size)
+        for i in range(self._L.effocr_effnet_num_params(self._h)):
+            name = self._L.effocr_effnet_param_name(self._h, i).decode()
+            t = sd[name].detach().to("cpu", torch.float32).contiguous()
+            _lib.effnet_check(self._L.effocr_effnet_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()),
+                              f"effocr_effnet_set_param({name})")
+        nbytes = int(self._L.effocr_effnet_weights_bytes(self._h))
+        with torch.cuda.device(self.device):
+            self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.effnet_check(self._L.effocr_effnet_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_effnet_upload")
+        self._ws = {}
+        self.split_streams = False
+        self._side = None
+        self._side_used = set()
+        self._stream_locks = {}
+        self._profiling = False
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and self._h.value:
+                self._L.effocr_effnet_destroy(self._h)
+                self._h = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def set_chunk(self, crops_per_chunk):
+        """Internal sub-batch size (0 = the library's default: a workspace within 512 MiB, at most 256 crops); effocr_effnet_set_chunk."""
+        _lib.effnet_check(self._L.effocr_effnet_set_chunk(self._h, int(crops_per_chunk)), "effocr_effnet_set_chunk")
+
+    def set_option(self, name, value):
+        raise ValueError(f"the EfficientNet encoder has no option {name!r}")
+
+    def workspace_bytes(self, batch):
+        return int(self._L.effocr_effnet_workspace_bytes(self._h, int(batch)))
+
+    @property
+    def crop_dtype(self):
+        return torch.float32
+
+    def _enqueue(self, x, emb, normalize, ws):
+        _lib.effnet_check(self._L.effocr_effnet_forward(self._h, _lib.ptr(x), _lib.PREC["fp32"], x.shape[0], _lib.ptr(emb),
+                                                        1 if normalize else 0, _lib.ptr(ws), ws.numel(),
+                                                        _lib.current_stream(self.device)), "effocr_effnet_forward")
+
+    def check_status(self):
+        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
+        non-finite embedding (the status word is sticky; this call clears it)."""
+        with self._lock, torch.cuda.device(self.device):
+            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
+            if ws is None:
+                return
+            _lib.effnet_check(self._L.effocr_effnet_check_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
+                              "effocr_effnet_check_status")
+
+    def reset_status(self):
+        """Clear the current stream's status word without reading it (asynchronous)."""
+        with self._lock, torch.cuda.device(self.device):
+            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
+            if ws is not None:
+                _lib.effnet_check(self._L.effocr_effnet_reset_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
+                                  "effocr_effnet_reset_status")
+
+    def profile_begin(self, only=None):
+        raise NotImplementedError("the EfficientNet encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+
+    def profile_collect(self):
+        raise NotImplementedError("the EfficientNet encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+
+
 def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
     """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, ResNetEncoder (libeffocr_resnet.so) for resnet34 / resnet50,
-    MobileNetV3Encoder (libeffocr_mnv3.so) for mobilenetv3_small_075 / _small_100 / _large_100, HipEncoder (libeffocr_hip.so) for every
-    other architecture (mobilenetv3_small_050 among them)."""
+    MobileNetV3Encoder (libeffocr_mnv3.so) for mobilenetv3_small_075 / _small_100 / _large_100, EfficientNetEncoder
+    (libeffocr_effnet.so) for efficientnet_b0 / tf_efficientnet_b0, HipEncoder (libeffocr_hip.so) for every other architecture
+    (mobilenetv3_small_050 among them)."""
     cls = (SwinEncoder if W.is_swin(arch) else ResNetEncoder if W.is_resnet_lib(arch) else MobileNetV3Encoder if W.is_mnv3_lib(arch)
-           else HipEncoder)
+           else EfficientNetEncoder if W.is_efficientnet(arch) else HipEncoder)
     return cls(arch, state_dict, img_size=img_size, precision=precision, device=device)
 
 
@@ -515,8 +603,8 @@ def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size
 
     Only the ``"timm"`` backend is implemented, with the architectures BASELINE.json names (resnet18, vit_small_patch16_224,
     vit_base_patch16_224), ``convnext_tiny`` and ``mobilenetv3_small_050`` (recommended by the reference README for
-    ``--auto_model_timm``), ``swin_tiny_patch4_window7_224``, ``resnet34``, ``resnet50``, ``mobilenetv3_small_075``, ``mobilenetv3_small_100`` and
-    ``mobilenetv3_large_100`` (the "hf" branch and XcitDinoEncoder are out
+    ``--auto_model_timm``), ``swin_tiny_patch4_window7_224``, ``resnet34``, ``resnet50``, ``mobilenetv3_small_075``, ``mobilenetv3_small_100``,
+    ``mobilenetv3_large_100``, ``efficientnet_b0`` and ``tf_efficientnet_b0`` (the "hf" branch and XcitDinoEncoder are out
     of scope); anything else raises NotImplementedError exactly like the reference's ``else`` branch
     (encoders.py:93-95).
     ``precision`` / ``img_size`` are extensions with reference-compatible defaults.

@@ -19,6 +19,13 @@ MobileNetV3 (``mobilenetv3_small_050`` / ``_075`` / ``_100``, ``mobilenetv3_larg
 ``blocks.i.j.{conv_pw,bn1,conv_dw,bn2,se.conv_reduce,se.conv_expand,conv_pwl,bn3}``, ``conv_head``); the
 builder is pinned by the parameter counts of three widths (tests/test_mobilenetv3_host.py).
 
+EfficientNet-B0 (``efficientnet_b0`` / ``tf_efficientnet_b0``) comes out of the same timm builder: timm ``efficientnet.py``,
+``_gen_efficientnet`` at multipliers 1.0 / 1.0 (``efficientnet_blocks``) — a 32-channel stem, squeeze-excite in all 16 blocks at
+``round(0.25 x the block's input channels)``, ``conv_head`` (no bias) + ``bn2`` + SiLU before the pool.  The two names share keys and
+shapes; the ``tf_`` variant (BN eps 1e-3, TensorFlow SAME padding) cannot be told from a checkpoint and must be named.  The key names
+come from timm's source as remembered and are UNVERIFIED against a timm install; the architecture is pinned against
+``transformers.EfficientNetModel`` (tests/test_efficientnet_host.py).
+
 Swin-T (``swin_tiny_patch4_window7_224``) key names follow timm's ``swin_transformer.py`` as of timm 0.9
 (``patch_embed.proj`` / ``patch_embed.norm``, ``layers.i.blocks.j.{norm1,attn.relative_position_bias_table,attn.qkv,attn.proj,
 norm2,mlp.fc1,mlp.fc2}``, the patch merging ``layers.i.downsample.{norm,reduction}`` at the START of stages 1-3, ``norm``, classifier
@@ -76,6 +83,24 @@ MOBILENETV3_LARGE_ARCH_DEF = (
     ("ir_r3_k5_s2_e6_c160_se0.25",),
     ("cn_r1_k1_s1_c960",),
 )
+EFFICIENTNET_CFG = {
+    # name: (BN eps, TensorFlow SAME padding) — timm efficientnet.py _gen_efficientnet(channel_multiplier=1.0, depth_multiplier=1.0); both
+    # run on libeffocr_effnet.so.  b1-b7, efficientnet_lite*, efficientnetv2_* and the _ns / _ap weight tags are not supported.
+    "efficientnet_b0": (1e-5, False),
+    "tf_efficientnet_b0": (1e-3, True),
+}
+EFFICIENTNET_ARCH_DEF = (
+    # timm's arch-def strings for EfficientNet-B0: every block SiLU, squeeze-excite 0.25 of the block's INPUT channels
+    ("ds_r1_k3_s1_e1_c16_se0.25",),
+    ("ir_r2_k3_s2_e6_c24_se0.25",),
+    ("ir_r2_k5_s2_e6_c40_se0.25",),
+    ("ir_r3_k3_s2_e6_c80_se0.25",),
+    ("ir_r3_k5_s1_e6_c112_se0.25",),
+    ("ir_r4_k5_s2_e6_c192_se0.25",),
+    ("ir_r1_k3_s1_e6_c320_se0.25",),
+)
+EFFICIENTNET_STEM = 32
+EFFICIENTNET_FEATURES = 1280          # conv_head width of EfficientNet-B0
 SWIN_CFG = {
     # name: (embed_dim, depths, heads, window) — timm swin_transformer.py; head dim 32 in every stage, mlp ratio 4, patch 4
     "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24), 7),
@@ -94,6 +119,16 @@ def make_divisible(v, divisor=8, min_value=None, round_limit=0.9):
     return new_v
 
 
+def _parse_block_def(bs):
+    """One timm arch-def string, e.g. "ir_r2_k5_s1_e6_c40_se0.25_nre" -> ("ir", {"r": "2", "k": "5", ..., "nre": ""})."""
+    ops = bs.split("_")
+    opt = {}
+    for o in ops[1:]:
+        m = re.match(r"([a-z]+)([0-9.]*)$", o)
+        opt[m.group(1)] = m.group(2)
+    return ops[0], opt
+
+
 def mobilenetv3_blocks(arch):
     """(stem channels, [block dicts], head width) of a MobileNetV3 (Small or Large, chosen by name), built from MOBILENETV3_ARCH_DEF /
     MOBILENETV3_LARGE_ARCH_DEF the way timm's _efficientnet_builder does.  A block dict has: key (e.g. "blocks.2.1"), type ("ds" | "ir" | "cn"), cin, mid, cout, k, stride,
@@ -105,27 +140,51 @@ def mobilenetv3_blocks(arch):
     for si, stage in enumerate(MOBILENETV3_LARGE_ARCH_DEF if large else MOBILENETV3_ARCH_DEF):
         bi = 0
         for bs in stage:
-            ops = bs.split("_")
-            opt = {}
-            for o in ops[1:]:
-                m = re.match(r"([a-z]+)([0-9.]*)$", o)
-                opt[m.group(1)] = m.group(2)
+            kind, opt = _parse_block_def(bs)
             for r in range(int(opt["r"])):
                 cout = make_divisible(int(opt["c"]) * mult)
                 stride = int(opt["s"]) if r == 0 else 1
                 k = int(opt["k"])
-                if ops[0] == "ds":
+                if kind == "ds":
                     mid = cin
-                elif ops[0] == "ir":
+                elif kind == "ir":
                     mid = make_divisible(cin * float(opt["e"]))
                 else:
                     mid = cout
                 se = make_divisible(mid * float(opt["se"])) if "se" in opt else 0
-                blocks.append(dict(key=f"blocks.{si}.{bi}", type=ops[0], cin=cin, mid=mid, cout=cout, k=k, stride=stride, se=se,
-                                   hs="nre" not in opt, res=(ops[0] != "cn" and stride == 1 and cin == cout)))
+                blocks.append(dict(key=f"blocks.{si}.{bi}", type=kind, cin=cin, mid=mid, cout=cout, k=k, stride=stride, se=se,
+                                   hs="nre" not in opt, res=(kind != "cn" and stride == 1 and cin == cout)))
                 cin = cout
                 bi += 1
     return stem, blocks, MOBILENETV3_LARGE_FEATURES if large else MOBILENETV3_FEATURES
+
+
+def efficientnet_blocks(arch):
+    """(stem channels, [block dicts], head width) of an EfficientNet-B0, built from EFFICIENTNET_ARCH_DEF the way timm's
+    _efficientnet_builder does at multipliers 1.0 / 1.0.  A block dict has the keys of mobilenetv3_blocks' (hs is False: every activation
+    is SiLU); it differs in the squeeze-excite width, ``round(cin x ratio)`` of the block's INPUT channels without make_divisible, and in
+    having no "cn" stage."""
+    if arch not in EFFICIENTNET_CFG:
+        raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+    blocks, cin = [], EFFICIENTNET_STEM
+    for si, stage in enumerate(EFFICIENTNET_ARCH_DEF):
+        bi = 0
+        for bs in stage:
+            kind, opt = _parse_block_def(bs)
+            for r in range(int(opt["r"])):
+                cout = make_divisible(int(opt["c"]))
+                stride = int(opt["s"]) if r == 0 else 1
+                mid = cin if kind == "ds" else make_divisible(cin * float(opt["e"]))
+                blocks.append(dict(key=f"blocks.{si}.{bi}", type=kind, cin=cin, mid=mid, cout=cout, k=int(opt["k"]), stride=stride,
+                                   se=int(round(cin * float(opt["se"]))), hs=False, res=(stride == 1 and cin == cout)))
+                cin = cout
+                bi += 1
+    return EFFICIENTNET_STEM, blocks, EFFICIENTNET_FEATURES
+
+
+def is_efficientnet(arch):
+    """efficientnet_b0 / tf_efficientnet_b0: the encoders that run on libeffocr_effnet.so."""
+    return arch in EFFICIENTNET_CFG
 
 
 def is_mobilenetv3(arch):
@@ -157,6 +216,8 @@ def embed_dim(arch):
         return MOBILENETV3_LARGE_FEATURES if is_mobilenetv3_large(arch) else MOBILENETV3_FEATURES
     if arch in SWIN_CFG:
         return SWIN_CFG[arch][0] * 8
+    if arch in EFFICIENTNET_CFG:
+        return EFFICIENTNET_FEATURES
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -182,10 +243,11 @@ def is_convnext(arch):
 # (models/classifiers.py:35-83).  Its input is the encoder's embedding before L2 normalisation (HipEncoder.forward(x, normalize=False)):
 # resnet18 the global-pooled features, ViT norm(x)[:, 0] (fc_norm is Identity for token pooling), convnext_tiny the output of head.norm,
 # mobilenetv3 conv_head + hard-swish.
+# efficientnet_b0 / tf_efficientnet_b0: the global average pool of SiLU(bn2(conv_head)).
 # swin_tiny_patch4_window7_224: the mean of the final norm's tokens (timm >= 0.9 names the head head.fc; strip_prefix renames timm < 0.9's head).
 HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bias"),
              "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias"),
-             "swin": ("head.fc.weight", "head.fc.bias")}
+             "swin": ("head.fc.weight", "head.fc.bias"), "efficientnet": ("classifier.weight", "classifier.bias")}
 
 
 def _family(arch):
@@ -199,6 +261,8 @@ def _family(arch):
         return "mobilenetv3"
     if arch in SWIN_CFG:
         return "swin"
+    if arch in EFFICIENTNET_CFG:
+        return "efficientnet"
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -317,6 +381,8 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _mobilenetv3_shapes(arch)
     if arch in SWIN_CFG:
         return _swin_shapes(arch)
+    if arch in EFFICIENTNET_CFG:
+        return _efficientnet_shapes(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -401,6 +467,52 @@ def _mobilenetv3_shapes(arch, num_classes=0):
     return s
 
 
+def _efficientnet_shapes(arch, num_classes=0):
+    """timm's state-dict order, as _mobilenetv3_shapes; conv_head has no bias and is followed by bn2."""
+    s = OrderedDict()
+
+    def bn(p, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{p}.{leaf}"] = (c,)
+
+    def se(p, c, r):
+        s[p + ".se.conv_reduce.weight"] = (r, c, 1, 1)
+        s[p + ".se.conv_reduce.bias"] = (r,)
+        s[p + ".se.conv_expand.weight"] = (c, r, 1, 1)
+        s[p + ".se.conv_expand.bias"] = (c,)
+    stem, blocks, nf = efficientnet_blocks(arch)
+    s["conv_stem.weight"] = (stem, 3, 3, 3)
+    bn("bn1", stem)
+    for b in blocks:
+        p = b["key"]
+        if b["type"] == "ds":
+            s[p + ".conv_dw.weight"] = (b["cin"], 1, b["k"], b["k"])
+            bn(p + ".bn1", b["cin"])
+            se(p, b["cin"], b["se"])
+            s[p + ".conv_pw.weight"] = (b["cout"], b["cin"], 1, 1)
+            bn(p + ".bn2", b["cout"])
+        else:
+            s[p + ".conv_pw.weight"] = (b["mid"], b["cin"], 1, 1)
+            bn(p + ".bn1", b["mid"])
+            s[p + ".conv_dw.weight"] = (b["mid"], 1, b["k"], b["k"])
+            bn(p + ".bn2", b["mid"])
+            se(p, b["mid"], b["se"])
+            s[p + ".conv_pwl.weight"] = (b["cout"], b["mid"], 1, 1)
+            bn(p + ".bn3", b["cout"])
+    s["conv_head.weight"] = (nf, blocks[-1]["cout"], 1, 1)
+    bn("bn2", nf)
+    if num_classes:
+        s["classifier.weight"] = (num_classes, nf)
+        s["classifier.bias"] = (num_classes,)
+    return s
+
+
+def efficientnet_num_learnable(arch, num_classes=0):
+    """Learnable parameters (BN running statistics excluded) of the builder's table, with an optional classifier."""
+    return sum(math.prod(shp) for k, shp in _efficientnet_shapes(arch, num_classes).items()
+               if not k.endswith(("running_mean", "running_var")))
+
+
 def mobilenetv3_num_learnable(arch, num_classes=0):
     """Learnable parameters (BN running statistics excluded) of the builder's table, with an optional classifier."""
     n = 0
@@ -418,7 +530,7 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
     LN/BN affine terms and running statistics, so that attention is far from uniform and every
     term of every kernel (biases, gamma/beta, BN folding) is exercised by the parity tests.
     The generator is the CPU Philox stream, identical on every machine with this torch build.
-    ConvNeXt (_init_convnext) and MobileNetV3 (_init_mobilenetv3) draw from generators of their own with rules of their own.
+    ConvNeXt (_init_convnext) and MobileNetV3 / EfficientNet-B0 (_init_mobilenetv3) draw from generators of their own with rules of their own.
     ``num_classes`` > 0 appends timm's classifier head, drawn from a generator of its own (init_head): the encoder's
     parameters are the same with and without a head.
     """
@@ -428,7 +540,7 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return sd
     if arch in CONVNEXT_CFG:
         return _init_convnext(arch, seed, img_size, scale)
-    if arch in MOBILENETV3_CFG:
+    if arch in MOBILENETV3_CFG or arch in EFFICIENTNET_CFG:
         return _init_mobilenetv3(arch, seed, img_size, scale)
     if arch in SWIN_CFG:
         return _init_swin(arch, seed, img_size, scale)
@@ -524,7 +636,7 @@ def _init_convnext(arch, seed, img_size, scale):
 
 
 def _init_mobilenetv3(arch, seed, img_size, scale):
-    """MobileNetV3 seeded init.  scale="timm": timm's _init_weight_goog (convs N(0, sqrt(2 / fan_out)) with fan_out = k*k*out / groups,
+    """MobileNetV3 (and EfficientNet-B0: the same builder's key names and shapes) seeded init.  scale="timm": timm's _init_weight_goog (convs N(0, sqrt(2 / fan_out)) with fan_out = k*k*out / groups,
     zero biases, BN at identity with running statistics 0 / 1).  scale="unit": fan-in-scaled convs, BN gains U(0.5, 1.5), shifts and
     running means N(0, 0.1), running variances U(0.5, 2.0), conv biases N(0, 0.1): every term of the BN folding is exercised."""
     g = torch.Generator(device="cpu")
@@ -735,6 +847,14 @@ def infer_arch(sd):
             want = param_shapes(name)
             if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
                 return name
+    if ("conv_stem.weight" in sd and "conv_head.weight" in sd and "bn2.weight" in sd and "conv_head.bias" not in sd
+            and sd["conv_stem.weight"].shape[0] == EFFICIENTNET_STEM):
+        # conv_head without a bias, followed by bn2, behind a 32-channel stem: EfficientNet.  tf_efficientnet_b0 has the same keys and
+        # shapes (it differs in BN eps and padding) and must be named by the caller
+        want = param_shapes("efficientnet_b0")
+        if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
+            return "efficientnet_b0"
+        raise ValueError("unsupported EfficientNet: only efficientnet_b0 / tf_efficientnet_b0 shapes are supported")
     if "conv_stem.weight" in sd and "conv_head.weight" in sd:
         # Large has a seventh stage (blocks.6.0, the 960-wide ConvBnAct), Small ends at blocks.5.0; the width follows from the shapes
         large = "blocks.6.0.conv.weight" in sd
