@@ -173,175 +173,130 @@ def lib():
     return _lib
 
 
-# libeffocr_head.so (include/effocr_head.h): the FFNN classifier head, a library of its own because libeffocr_hip.so is at its size cap.
-# Bound by head_lib(); its functions are not part of EXPORTS (the product library's ABI, checked against effocr_hip.h).
+# The optional capabilities ship as shared objects of their own, because libeffocr_hip.so is at its size cap (DESIGN.md "Library split"):
+# each has its own header, ABI version and last_error, exports effocr_<prefix>_* and is bound by <prefix>_lib() below.  None of their
+# functions is part of EXPORTS (the product library's ABI, checked against effocr_hip.h).
+_family = {}             # prefix -> handle
+
+
+def _load_family(so_path, prefix, abi_version, signatures, label):
+    """Load (once) and return the ctypes handle of the library at ``so_path``; raises if it is missing or its ABI version differs."""
+    with _lock:
+        handle = _family.get(prefix)
+        if handle is None:
+            if not os.path.exists(so_path):
+                raise EffOCRHipError(f"{so_path} not found: the {label} library is required (no CPU fallback). "
+                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
+            handle = ctypes.CDLL(so_path)
+            for name, (res, args) in signatures.items():
+                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
+                fn.restype, fn.argtypes = res, args
+            got = getattr(handle, f"effocr_{prefix}_abi_version")()
+            if got != abi_version:
+                raise EffOCRHipError(f"{os.path.basename(so_path)} ABI version {got} != {abi_version} expected by this package: rebuild "
+                                     "(make -C effocr_amd/csrc)")
+            _family[prefix] = handle
+    return handle
+
+
+def _family_check(prefix):
+    def check(rc, what=""):
+        if rc != 0:
+            msg = getattr(globals()[f"{prefix}_lib"](), f"effocr_{prefix}_last_error")()
+            raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+    check.__name__ = f"{prefix}_check"
+    return check
+
+
+# libeffocr_head.so (include/effocr_head.h): the FFNN classifier head.
 HEAD_SO_PATH = os.path.join(_HERE, "libeffocr_head.so")
 HEAD_ABI_VERSION = 1     # == EFFOCR_HEAD_ABI_VERSION of include/effocr_head.h
 HEAD_EXPORTS = ("effocr_head_abi_version", "effocr_head_last_error", "effocr_classifier_head_workspace_bytes",
                 "effocr_classifier_head")
-_head = None
 
 
-def head_lib():
-    """Load (once) and return the ctypes handle of libeffocr_head.so; raises if it is missing or its ABI version differs."""
-    global _head
-    with _lock:
-        if _head is None:
-            if not os.path.exists(HEAD_SO_PATH):
-                raise EffOCRHipError(f"{HEAD_SO_PATH} not found: the classifier head library is required (no CPU fallback). "
-                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
-            c = ctypes
-            handle = c.CDLL(HEAD_SO_PATH)
-            sig = {
-                "effocr_head_abi_version": (c.c_int, []),
-                "effocr_head_last_error": (c.c_char_p, []),
-                "effocr_classifier_head_workspace_bytes": (c.c_size_t, [c.c_int64, c.c_int]),
-                "effocr_classifier_head": (c.c_int, [c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p,
-                                                     c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]),
-            }
-            for name in HEAD_EXPORTS:
-                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
-                fn.restype, fn.argtypes = sig[name]
-            got = handle.effocr_head_abi_version()
-            if got != HEAD_ABI_VERSION:
-                raise EffOCRHipError(f"libeffocr_head.so ABI version {got} != {HEAD_ABI_VERSION} expected by this package: rebuild "
-                                     "(make -C effocr_amd/csrc)")
-            _head = handle
-    return _head
-
-
-# libeffocr_swin.so (include/effocr_swin.h): the Swin-T encoder, a library of its own for the same reason (it carries its own copy of
-# the GEMMs, hidden).  Bound by swin_lib(); its functions are not part of EXPORTS either.
-SWIN_SO_PATH = os.path.join(_HERE, "libeffocr_swin.so")
-SWIN_ABI_VERSION = 1     # == EFFOCR_SWIN_ABI_VERSION of include/effocr_swin.h
-_swin = None
-
-
-def _swin_signatures():
+def _head_signatures():
     c = ctypes
-    vp, i32, i64, sz = c.c_void_p, c.c_int, c.c_int64, c.c_size_t
     return {
-        "effocr_swin_abi_version": (i32, []),
-        "effocr_swin_last_error": (c.c_char_p, []),
-        "effocr_swin_create": (i32, [c.c_char_p, i32, i32, c.POINTER(vp)]),
-        "effocr_swin_destroy": (None, [vp]),
-        "effocr_swin_embed_dim": (i32, [vp]),
-        "effocr_swin_num_params": (i32, [vp]),
-        "effocr_swin_param_name": (c.c_char_p, [vp, i32]),
-        "effocr_swin_param_numel": (i64, [vp, i32]),
-        "effocr_swin_set_param": (i32, [vp, c.c_char_p, vp, i64]),
-        "effocr_swin_weights_bytes": (sz, [vp]),
-        "effocr_swin_upload": (i32, [vp, vp, sz]),
-        "effocr_swin_workspace_bytes": (sz, [vp, i32]),
-        "effocr_swin_set_chunk": (i32, [vp, i32]),
-        "effocr_swin_forward": (i32, [vp, vp, i32, vp, i32, vp, sz, vp]),
-        "effocr_swin_check_status": (i32, [vp, vp, vp]),
+        "effocr_head_abi_version": (c.c_int, []),
+        "effocr_head_last_error": (c.c_char_p, []),
+        "effocr_classifier_head_workspace_bytes": (c.c_size_t, [c.c_int64, c.c_int]),
+        "effocr_classifier_head": (c.c_int, [c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p,
+                                             c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]),
     }
 
 
-SWIN_EXPORTS = tuple(sorted(_swin_signatures()))
+def head_lib():
+    return _load_family(HEAD_SO_PATH, "head", HEAD_ABI_VERSION, _head_signatures(), "classifier head")
+
+
+# libeffocr_swin.so (include/effocr_swin.h): the Swin-T encoder (it carries its own copy of the GEMMs, hidden).
+SWIN_SO_PATH = os.path.join(_HERE, "libeffocr_swin.so")
+SWIN_ABI_VERSION = 1     # == EFFOCR_SWIN_ABI_VERSION of include/effocr_swin.h
+
+
+def _encoder_signatures(prefix):
+    """The entry points every encoder-family library exports (csrc/enc_core.hpp holds their shared bodies)."""
+    c = ctypes
+    vp, i32, i64, sz = c.c_void_p, c.c_int, c.c_int64, c.c_size_t
+    return {f"effocr_{prefix}_{k}": v for k, v in {
+        "abi_version": (i32, []),
+        "last_error": (c.c_char_p, []),
+        "create": (i32, [c.c_char_p, i32, i32, c.POINTER(vp)]),
+        "destroy": (None, [vp]),
+        "embed_dim": (i32, [vp]),
+        "num_params": (i32, [vp]),
+        "param_name": (c.c_char_p, [vp, i32]),
+        "param_numel": (i64, [vp, i32]),
+        "set_param": (i32, [vp, c.c_char_p, vp, i64]),
+        "weights_bytes": (sz, [vp]),
+        "upload": (i32, [vp, vp, sz]),
+        "workspace_bytes": (sz, [vp, i32]),
+        "set_chunk": (i32, [vp, i32]),
+        "forward": (i32, [vp, vp, i32, vp, i32, vp, sz, vp]),
+        "check_status": (i32, [vp, vp, vp]),
+    }.items()}
+
+
+SWIN_EXPORTS = tuple(sorted(_encoder_signatures("swin")))
 
 
 def swin_lib():
-    """Load (once) and return the ctypes handle of libeffocr_swin.so; raises if it is missing or its ABI version differs."""
-    global _swin
-    with _lock:
-        if _swin is None:
-            if not os.path.exists(SWIN_SO_PATH):
-                raise EffOCRHipError(f"{SWIN_SO_PATH} not found: the Swin encoder library is required (no CPU fallback). "
-                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
-            handle = ctypes.CDLL(SWIN_SO_PATH)
-            for name, (res, args) in _swin_signatures().items():
-                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
-                fn.restype, fn.argtypes = res, args
-            got = handle.effocr_swin_abi_version()
-            if got != SWIN_ABI_VERSION:
-                raise EffOCRHipError(f"libeffocr_swin.so ABI version {got} != {SWIN_ABI_VERSION} expected by this package: rebuild "
-                                     "(make -C effocr_amd/csrc)")
-            _swin = handle
-    return _swin
+    return _load_family(SWIN_SO_PATH, "swin", SWIN_ABI_VERSION, _encoder_signatures("swin"), "Swin encoder")
 
 
-# libeffocr_resnet.so (include/effocr_resnet.h): the ResNet-34 / ResNet-50 encoders, a library of its own for the same reason (it carries its
-# own copy of resnet18's fp32 convolution pipeline, hidden).  Bound by resnet_lib(); its functions are not part of EXPORTS either.
+# libeffocr_resnet.so (include/effocr_resnet.h): the ResNet-34 / ResNet-50 encoders (it carries its own copy of resnet18's fp32
+# convolution pipeline, hidden).
 RESNET_SO_PATH = os.path.join(_HERE, "libeffocr_resnet.so")
 RESNET_ABI_VERSION = 1     # == EFFOCR_RESNET_ABI_VERSION of include/effocr_resnet.h
-_resnet = None
-
-
-def _resnet_signatures():
-    return {k.replace("effocr_swin_", "effocr_resnet_"): v for k, v in _swin_signatures().items()}
-
-
-RESNET_EXPORTS = tuple(sorted(_resnet_signatures()))
+RESNET_EXPORTS = tuple(sorted(_encoder_signatures("resnet")))
 
 
 def resnet_lib():
-    """Load (once) and return the ctypes handle of libeffocr_resnet.so; raises if it is missing or its ABI version differs."""
-    global _resnet
-    with _lock:
-        if _resnet is None:
-            if not os.path.exists(RESNET_SO_PATH):
-                raise EffOCRHipError(f"{RESNET_SO_PATH} not found: the ResNet encoder library is required (no CPU fallback). "
-                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
-            handle = ctypes.CDLL(RESNET_SO_PATH)
-            for name, (res, args) in _resnet_signatures().items():
-                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
-                fn.restype, fn.argtypes = res, args
-            got = handle.effocr_resnet_abi_version()
-            if got != RESNET_ABI_VERSION:
-                raise EffOCRHipError(f"libeffocr_resnet.so ABI version {got} != {RESNET_ABI_VERSION} expected by this package: rebuild "
-                                     "(make -C effocr_amd/csrc)")
-            _resnet = handle
-    return _resnet
+    return _load_family(RESNET_SO_PATH, "resnet", RESNET_ABI_VERSION, _encoder_signatures("resnet"), "ResNet encoder")
 
 
-# libeffocr_mnv3.so (include/effocr_mnv3.h): the MobileNetV3 small_075 / small_100 / large_100 encoders, a library of its own for the same
-# reason (a forward of its own, activations in HBM between blocks).  Bound by mnv3_lib(); its functions are not part of EXPORTS either.
+# libeffocr_mnv3.so (include/effocr_mnv3.h): the MobileNetV3 small_075 / small_100 / large_100 encoders (a forward of its own,
+# activations in HBM between blocks).
 MNV3_SO_PATH = os.path.join(_HERE, "libeffocr_mnv3.so")
 MNV3_ABI_VERSION = 1     # == EFFOCR_MNV3_ABI_VERSION of include/effocr_mnv3.h
-_mnv3 = None
-
-
-def _mnv3_signatures():
-    return {k.replace("effocr_swin_", "effocr_mnv3_"): v for k, v in _swin_signatures().items()}
-
-
-MNV3_EXPORTS = tuple(sorted(_mnv3_signatures()))
+MNV3_EXPORTS = tuple(sorted(_encoder_signatures("mnv3")))
 
 
 def mnv3_lib():
-    """Load (once) and return the ctypes handle of libeffocr_mnv3.so; raises if it is missing or its ABI version differs."""
-    global _mnv3
-    with _lock:
-        if _mnv3 is None:
-            if not os.path.exists(MNV3_SO_PATH):
-                raise EffOCRHipError(f"{MNV3_SO_PATH} not found: the MobileNetV3 encoder library is required (no CPU fallback). "
-                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
-            handle = ctypes.CDLL(MNV3_SO_PATH)
-            for name, (res, args) in _mnv3_signatures().items():
-                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
-                fn.restype, fn.argtypes = res, args
-            got = handle.effocr_mnv3_abi_version()
-            if got != MNV3_ABI_VERSION:
-                raise EffOCRHipError(f"libeffocr_mnv3.so ABI version {got} != {MNV3_ABI_VERSION} expected by this package: rebuild "
-                                     "(make -C effocr_amd/csrc)")
-            _mnv3 = handle
-    return _mnv3
+    return _load_family(MNV3_SO_PATH, "mnv3", MNV3_ABI_VERSION, _encoder_signatures("mnv3"), "MobileNetV3 encoder")
 
 
-# libeffocr_effnet.so (include/effocr_effnet.h): the EfficientNet-B0 encoders efficientnet_b0 / tf_efficientnet_b0, a library of its own for
-# the same reason (its own stem, depthwise and squeeze-excite kernels, plus a hidden copy of libeffocr_mnv3.so's pointwise GEMM).  Bound by
-# effnet_lib(); its functions are not part of EXPORTS either.
+# libeffocr_effnet.so (include/effocr_effnet.h): the EfficientNet-B0 encoders efficientnet_b0 / tf_efficientnet_b0 (its own stem,
+# depthwise and squeeze-excite kernels, plus a hidden copy of libeffocr_mnv3.so's pointwise GEMM).
 EFFNET_SO_PATH = os.path.join(_HERE, "libeffocr_effnet.so")
 EFFNET_ABI_VERSION = 1     # == EFFOCR_EFFNET_ABI_VERSION of include/effocr_effnet.h
-_effnet = None
 
 
 def _effnet_signatures():
     c = ctypes
     vp, i32 = c.c_void_p, c.c_int
-    sig = {k.replace("effocr_swin_", "effocr_effnet_"): v for k, v in _swin_signatures().items()}
+    sig = _encoder_signatures("effnet")
     sig["effocr_effnet_forward"] = (i32, [vp, vp, i32, i32, vp, i32, vp, c.c_size_t, vp])      # (the crop type after the crops)
     sig["effocr_effnet_reset_status"] = (i32, [vp, vp, vp])
     sig["effocr_effnet_op_tiles"] = (i32, [i32])                                                # test entry points
@@ -354,53 +309,14 @@ EFFNET_EXPORTS = tuple(sorted(_effnet_signatures()))
 
 
 def effnet_lib():
-    """Load (once) and return the ctypes handle of libeffocr_effnet.so; raises if it is missing or its ABI version differs."""
-    global _effnet
-    with _lock:
-        if _effnet is None:
-            if not os.path.exists(EFFNET_SO_PATH):
-                raise EffOCRHipError(f"{EFFNET_SO_PATH} not found: the EfficientNet encoder library is required (no CPU fallback). "
-                                     "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C effocr_amd/csrc`.")
-            handle = ctypes.CDLL(EFFNET_SO_PATH)
-            for name, (res, args) in _effnet_signatures().items():
-                fn = getattr(handle, name)           # AttributeError if the symbol is not exported
-                fn.restype, fn.argtypes = res, args
-            got = handle.effocr_effnet_abi_version()
-            if got != EFFNET_ABI_VERSION:
-                raise EffOCRHipError(f"libeffocr_effnet.so ABI version {got} != {EFFNET_ABI_VERSION} expected by this package: rebuild "
-                                     "(make -C effocr_amd/csrc)")
-            _effnet = handle
-    return _effnet
+    return _load_family(EFFNET_SO_PATH, "effnet", EFFNET_ABI_VERSION, _effnet_signatures(), "EfficientNet encoder")
 
 
-def effnet_check(rc, what=""):
-    if rc != 0:
-        msg = effnet_lib().effocr_effnet_last_error()
-        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
-
-
-def mnv3_check(rc, what=""):
-    if rc != 0:
-        msg = mnv3_lib().effocr_mnv3_last_error()
-        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
-
-
-def resnet_check(rc, what=""):
-    if rc != 0:
-        msg = resnet_lib().effocr_resnet_last_error()
-        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
-
-
-def swin_check(rc, what=""):
-    if rc != 0:
-        msg = swin_lib().effocr_swin_last_error()
-        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
-
-
-def head_check(rc, what=""):
-    if rc != 0:
-        msg = head_lib().effocr_head_last_error()
-        raise EffOCRHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+head_check = _family_check("head")
+swin_check = _family_check("swin")
+resnet_check = _family_check("resnet")
+mnv3_check = _family_check("mnv3")
+effnet_check = _family_check("effnet")
 
 
 def check(rc, what="", handle=None):

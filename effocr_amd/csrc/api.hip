@@ -2,8 +2,7 @@
 // table, host-side packing / BatchNorm folding, forward orchestration) and thin wrappers over the
 // kernel launchers.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_hip.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "enc_core.hpp"
 
 
 #include <math.h>
@@ -15,28 +14,6 @@
 #include <vector>
 
 namespace effocr {
-
-static thread_local std::string g_err;
-
-void set_error(const std::string& msg) { g_err = msg; }
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return EFFOCR_OK;
-}
-
-int device_cus() {
-  static int cache[64] = {0};                            // benign race: every thread computes the same value
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cache[dev] == 0) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cache[dev] = v;
-  }
-  return cache[dev];
-}
 
 namespace {
 
@@ -126,11 +103,6 @@ void add_param(effocr_encoder* e, const std::string& name, std::vector<int64_t> 
   e->index[name] = (int)e->params.size();
   e->params.push_back(std::move(p));
 }
-
-struct Alloc {
-  size_t off = 0;
-  size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
 
 void build_vit(effocr_encoder* e) {
   const int D = e->vit.D, depth = e->vit.depth, mlp = e->vit.mlp;
@@ -361,22 +333,6 @@ int build_mobilenetv3(effocr_encoder* e) {
   e->wbytes = a.off;
   if (e->wbytes >= ((size_t)1 << 32)) return fail(EFFOCR_EUNSUPPORTED, "mobilenetv3: weight blob too large");
   return EFFOCR_OK;
-}
-
-uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                            // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
-
-void put_f32(std::vector<char>& blob, size_t off, const float* src, size_t n) { memcpy(blob.data() + off, src, n * 4); }
-void put_op(std::vector<char>& blob, size_t off, const float* src, size_t n, int prec) {
-  if (prec == PREC_FP32) { memcpy(blob.data() + off, src, n * 4); return; }
-  uint16_t* d = reinterpret_cast<uint16_t*>(blob.data() + off);
-  if (prec == PREC_BF16) for (size_t i = 0; i < n; ++i) d[i] = f32_to_bf16(src[i]);
-  else for (size_t i = 0; i < n; ++i) d[i] = f32_to_f16(src[i]);
 }
 
 // [N,K] fp32 -> 16-bit fragment-blocked [N/32][K/8][32 rows][8 elements] (common.hpp blk_off); N % 32 == 0, K % 8 == 0
@@ -1081,8 +1037,6 @@ int resnet_forward(effocr_encoder* e, const float* x, int B, float* emb, int l2,
   }
   return global_avgpool_nhwc(bufs[cur], emb, B, H * H, 512, l2, s);
 }
-
-hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 
 }  // namespace
 }  // namespace effocr

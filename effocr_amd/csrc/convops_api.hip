@@ -5,8 +5,7 @@
 // All device pointers are caller-owned, `stream` is a hipStream_t (NULL = the default stream); every call returns 0 or a negative
 // EFFOCR_E* code (include/effocr_hip.h) whose message effocr_convops_last_error() holds for the calling thread.
 #include "../../include/effocr_hip.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "enc_core.hpp"
 #include "resnet16.hpp"
 
 #include <string>
@@ -16,27 +15,6 @@
 
 namespace effocr {
 
-// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
-static thread_local std::string g_convops_err;
-void set_error(const std::string& msg) { g_convops_err = msg; }
-int fail(int code, const std::string& msg) { g_convops_err = msg; return code; }
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return EFFOCR_OK;
-}
-int device_cus() {
-  static int cache[64] = {0};                            // benign race: every thread computes the same value
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cache[dev] == 0) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cache[dev] = v;
-  }
-  return cache[dev];
-}
-
 extern thread_local int convops_last_nw, convops_last_ksplit;   // resnet.hip under -DEFFOCR_CONVOPS
 
 }  // namespace effocr
@@ -44,7 +22,7 @@ extern thread_local int convops_last_nw, convops_last_ksplit;   // resnet.hip un
 using namespace effocr;
 
 CONVOPS_API int effocr_convops_abi_version(void) { return EFFOCR_CONVOPS_ABI_VERSION; }
-CONVOPS_API const char* effocr_convops_last_error(void) { return g_convops_err.c_str(); }
+CONVOPS_API const char* effocr_convops_last_error(void) { return g_err.c_str(); }
 CONVOPS_API int effocr_convops_device_cus(void) { return device_cus(); }
 // channel tile (32 / 64 / 128) and K split of the calling thread's last effocr_convops_conv2d launch (0, 0 before the first)
 CONVOPS_API void effocr_convops_last_dispatch(int* nw, int* ksplit) {

@@ -3,33 +3,15 @@
 // own error state.  The kernels are effnet.hip's (stem, depthwise + tile sums, squeeze-excite gate) and mnv3g.hip's (pointwise GEMM, pool,
 // normalise).  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_effnet.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "mbconv_pack.hpp"
 #include "mnv3g.hpp"
 #include "effnet.hpp"
 
-#include <math.h>
-#include <string.h>
-#include <algorithm>
-#include <map>
 #include <memory>
-#include <string>
-#include <vector>
 
 #define EFFNET_API extern "C" __attribute__((visibility("default")))
 
 namespace effocr {
-
-// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
-static thread_local std::string g_effnet_err;
-void set_error(const std::string& msg) { g_effnet_err = msg; }
-int fail(int code, const std::string& msg) { g_effnet_err = msg; return code; }
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return EFFOCR_OK;
-}
-
 namespace {
 
 // sub-batches: as many crops as keep the workspace within EF_WS_BUDGET, at most EF_MAX_CHUNK
@@ -38,25 +20,10 @@ constexpr int EF_MAX_CHUNK = 256;
 constexpr int EF_CHUNK_LIMIT = 65535;                       // crops are the grid's z dimension in ef_dw
 constexpr int EF_D = 1280;
 
-struct Param { std::string name; int64_t numel; std::vector<float> data; bool set; };
-struct ConvOff { size_t w = 0, b = 0; };
 enum { BLK_DS = 0, BLK_IR = 1 };
 // one block of the table: geometry and blob offsets (pw = expand, dw = depthwise, ser / see = squeeze-excite reduce / expand, pwl = project
 // — for the ds block its conv_pw)
 struct Block { std::string key; int type, cin, mid, cout, k, stride, se, res; ConvOff pw, dw, ser, see, pwl; };
-
-struct Alloc {
-  size_t off = 0;
-  size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
-
-uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                            // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
 
 // timm's arch definition (_gen_efficientnet), one row per stage: type, repeats, kernel, stride of the first repeat, expansion, channels.
 // Every block has squeeze-excite at ratio 0.25 of its INPUT channels; at multipliers 1.0 / 1.0 no count is rounded.
@@ -71,38 +38,14 @@ const DefRow DEF_B0[] = {
 
 using namespace effocr;
 
-struct effocr_effnet {
-  int img = 224, prec = PREC_FP16, chunk = 0;
+struct effocr_effnet : EncoderCore {
   bool tf = false;                     // TensorFlow SAME padding and BN eps 1e-3
-  std::vector<Param> params;
-  std::map<std::string, int> index;
   std::vector<Block> blocks;
   ConvOff stem, head;
-  size_t wbytes = 0;
-  const char* wdev = nullptr;
 };
 
 namespace effocr {
 namespace {
-
-void add_param(effocr_effnet* e, const std::string& name, int64_t numel) {
-  e->index[name] = (int)e->params.size();
-  e->params.push_back(Param{name, numel, {}, false});
-}
-void add_bn(effocr_effnet* e, const std::string& p, int c) {
-  add_param(e, p + ".weight", c); add_param(e, p + ".bias", c);
-  add_param(e, p + ".running_mean", c); add_param(e, p + ".running_var", c);
-}
-void add_se(effocr_effnet* e, const std::string& p, int c, int r) {
-  add_param(e, p + ".se.conv_reduce.weight", (int64_t)r * c); add_param(e, p + ".se.conv_reduce.bias", r);
-  add_param(e, p + ".se.conv_expand.weight", (int64_t)c * r); add_param(e, p + ".se.conv_expand.bias", c);
-}
-const std::vector<float>& P(const effocr_effnet* e, const std::string& n) { return e->params[e->index.at(n)].data; }
-
-size_t pw_bytes(const effocr_effnet* e, int N, int K) {
-  if (e->prec == PREC_FP32) return (size_t)N * K * 4;
-  return (size_t)align_up(N, 16) * align_up(K, 16) * 2;       // zero-padded to whole 16 x 16 MFMA tiles
-}
 
 // The block list the way timm's _efficientnet_builder derives it, the parameter table in timm's state-dict order (a module's own
 // parameters, then its children's) and the blob layout.
@@ -122,97 +65,62 @@ void build_effnet(effocr_effnet* e) {
     }
     ++stage;
   }
-  add_param(e, "conv_stem.weight", (int64_t)EF_STEM_C * 27);
-  add_bn(e, "bn1", EF_STEM_C);
+  e->add_param("conv_stem.weight", (int64_t)EF_STEM_C * 27);
+  e->add_bn("bn1", EF_STEM_C);
   for (const Block& b : e->blocks) {
     const std::string& p = b.key;
     if (b.type == BLK_DS) {
-      add_param(e, p + ".conv_dw.weight", (int64_t)b.cin * b.k * b.k); add_bn(e, p + ".bn1", b.cin);
+      e->add_param(p + ".conv_dw.weight", (int64_t)b.cin * b.k * b.k); e->add_bn(p + ".bn1", b.cin);
       add_se(e, p, b.cin, b.se);
-      add_param(e, p + ".conv_pw.weight", (int64_t)b.cout * b.cin); add_bn(e, p + ".bn2", b.cout);
+      e->add_param(p + ".conv_pw.weight", (int64_t)b.cout * b.cin); e->add_bn(p + ".bn2", b.cout);
     } else {
-      add_param(e, p + ".conv_pw.weight", (int64_t)b.mid * b.cin); add_bn(e, p + ".bn1", b.mid);
-      add_param(e, p + ".conv_dw.weight", (int64_t)b.mid * b.k * b.k); add_bn(e, p + ".bn2", b.mid);
+      e->add_param(p + ".conv_pw.weight", (int64_t)b.mid * b.cin); e->add_bn(p + ".bn1", b.mid);
+      e->add_param(p + ".conv_dw.weight", (int64_t)b.mid * b.k * b.k); e->add_bn(p + ".bn2", b.mid);
       add_se(e, p, b.mid, b.se);
-      add_param(e, p + ".conv_pwl.weight", (int64_t)b.cout * b.mid); add_bn(e, p + ".bn3", b.cout);
+      e->add_param(p + ".conv_pwl.weight", (int64_t)b.cout * b.mid); e->add_bn(p + ".bn3", b.cout);
     }
   }
-  add_param(e, "conv_head.weight", (int64_t)EF_D * cin);
-  add_bn(e, "bn2", EF_D);
+  e->add_param("conv_head.weight", (int64_t)EF_D * cin);
+  e->add_bn("bn2", EF_D);
 
   Alloc a;
   e->stem.w = a.take((size_t)27 * EF_STEM_C * 4); e->stem.b = a.take((size_t)EF_STEM_C * 4);
   for (Block& b : e->blocks) {
-    if (b.type == BLK_IR) { b.pw.w = a.take(pw_bytes(e, b.mid, b.cin)); b.pw.b = a.take((size_t)b.mid * 4); }
+    if (b.type == BLK_IR) { b.pw.w = a.take(pw_bytes(e->prec, b.mid, b.cin)); b.pw.b = a.take((size_t)b.mid * 4); }
     b.dw.w = a.take((size_t)b.k * b.k * b.mid * 4); b.dw.b = a.take((size_t)b.mid * 4);
     b.ser.w = a.take((size_t)b.se * b.mid * 4); b.ser.b = a.take((size_t)b.se * 4);
     b.see.w = a.take((size_t)b.mid * b.se * 4); b.see.b = a.take((size_t)b.mid * 4);
-    b.pwl.w = a.take(pw_bytes(e, b.cout, b.mid)); b.pwl.b = a.take((size_t)b.cout * 4);
+    b.pwl.w = a.take(pw_bytes(e->prec, b.cout, b.mid)); b.pwl.b = a.take((size_t)b.cout * 4);
   }
-  e->head.w = a.take(pw_bytes(e, EF_D, cin)); e->head.b = a.take((size_t)EF_D * 4);
+  e->head.w = a.take(pw_bytes(e->prec, EF_D, cin)); e->head.b = a.take((size_t)EF_D * 4);
   e->wbytes = a.off;
 }
-
-// pointwise weight [N][K] fp32 -> the blob: fp32 as it is, else rounded once to the operand type inside a zeroed [N16][K16] frame
-void put_pw(const effocr_effnet* e, std::vector<char>& blob, size_t off, const float* w, int N, int K) {
-  if (e->prec == PREC_FP32) { memcpy(blob.data() + off, w, (size_t)N * K * 4); return; }
-  const int Kp = (int)align_up(K, 16);
-  uint16_t* d = reinterpret_cast<uint16_t*>(blob.data() + off);   // (the blob starts zeroed)
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) d[(size_t)n * Kp + k] = e->prec == PREC_BF16 ? f32_to_bf16(w[(size_t)n * K + k]) : f32_to_f16(w[(size_t)n * K + k]);
-}
-void put_f32(std::vector<char>& blob, size_t off, const float* v, size_t n) { memcpy(blob.data() + off, v, n * 4); }
 
 // Every BatchNorm (eval; eps 1e-5, tf_: 1e-3) folded into the conv in front of it in fp32: w' = w g / sqrt(v + eps),
 // b' = beta - m g / sqrt(v + eps).  Depthwise and stem weights tap-major; SE reduce as it is, SE expand transposed to [R][C].
 void pack_effnet(const effocr_effnet* e, std::vector<char>& blob) {
-  const float eps = e->tf ? 1e-3f : 1e-5f;
-  std::vector<float> wf, bf;
-  auto fold = [&](const std::string& w, const std::string& bn) {
-    const auto& W = P(e, w);
-    const auto& g = P(e, bn + ".weight"); const auto& be = P(e, bn + ".bias");
-    const auto& m = P(e, bn + ".running_mean"); const auto& v = P(e, bn + ".running_var");
-    const size_t C = g.size(), per = W.size() / C;
-    wf.resize(W.size()); bf.resize(C);
-    for (size_t c = 0; c < C; ++c) {
-      const float sc = g[c] / sqrtf(v[c] + eps);
-      for (size_t k = 0; k < per; ++k) wf[c * per + k] = W[c * per + k] * sc;
-      bf[c] = be[c] - m[c] * sc;
-    }
-  };
-  auto pw = [&](const ConvOff& c, const std::string& w, const std::string& bn, int N, int K) {
-    fold(w, bn); put_pw(e, blob, c.w, wf.data(), N, K); put_f32(blob, c.b, bf.data(), bf.size());
-  };
-  auto tapmajor = [&](const ConvOff& c, const std::string& w, const std::string& bn, int C, int taps) {
-    fold(w, bn);
-    float* d = reinterpret_cast<float*>(blob.data() + c.w);
-    for (int ch = 0; ch < C; ++ch)
-      for (int t = 0; t < taps; ++t) d[(size_t)t * C + ch] = wf[(size_t)ch * taps + t];
-    put_f32(blob, c.b, bf.data(), bf.size());
-  };
-  tapmajor(e->stem, "conv_stem.weight", "bn1", EF_STEM_C, 27);           // [ci][ky][kx] taps
+  BnFolder f{e, blob, e->tf ? 1e-3f : 1e-5f};
+  f.tapmajor(e->stem, "conv_stem.weight", "bn1", EF_STEM_C, 27);           // [ci][ky][kx] taps
   for (const Block& b : e->blocks) {
     const std::string& p = b.key;
     if (b.type == BLK_DS) {
-      tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn1", b.cin, b.k * b.k);
-      pw(b.pwl, p + ".conv_pw.weight", p + ".bn2", b.cout, b.cin);
+      f.tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn1", b.cin, b.k * b.k);
+      f.pw(b.pwl, p + ".conv_pw.weight", p + ".bn2", b.cout, b.cin);
     } else {
-      pw(b.pw, p + ".conv_pw.weight", p + ".bn1", b.mid, b.cin);
-      tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn2", b.mid, b.k * b.k);
-      pw(b.pwl, p + ".conv_pwl.weight", p + ".bn3", b.cout, b.mid);
+      f.pw(b.pw, p + ".conv_pw.weight", p + ".bn1", b.mid, b.cin);
+      f.tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn2", b.mid, b.k * b.k);
+      f.pw(b.pwl, p + ".conv_pwl.weight", p + ".bn3", b.cout, b.mid);
     }
-    const auto& rw = P(e, p + ".se.conv_reduce.weight"); const auto& rb = P(e, p + ".se.conv_reduce.bias");
-    const auto& ew = P(e, p + ".se.conv_expand.weight"); const auto& eb = P(e, p + ".se.conv_expand.bias");
+    const auto& rw = e->P(p + ".se.conv_reduce.weight"); const auto& rb = e->P(p + ".se.conv_reduce.bias");
+    const auto& ew = e->P(p + ".se.conv_expand.weight"); const auto& eb = e->P(p + ".se.conv_expand.bias");
     put_f32(blob, b.ser.w, rw.data(), rw.size()); put_f32(blob, b.ser.b, rb.data(), rb.size());
     float* d = reinterpret_cast<float*>(blob.data() + b.see.w);
     for (int c = 0; c < b.mid; ++c)
       for (int j = 0; j < b.se; ++j) d[(size_t)j * b.mid + c] = ew[(size_t)c * b.se + j];
     put_f32(blob, b.see.b, eb.data(), eb.size());
   }
-  pw(e->head, "conv_head.weight", "bn2", EF_D, e->blocks.back().cout);
+  f.pw(e->head, "conv_head.weight", "bn2", EF_D, e->blocks.back().cout);
 }
-
-int out_size(int H, int stride) { return (H - 1) / stride + 1; }           // k x k, pad k / 2 or SAME
 
 // Workspace of one sub-batch of B crops: the status word; two block input / output maps (ping-pong); the expansion (at the block's input
 // resolution; conv_head's output too); the depthwise output; its tile sums; the squeeze-excite gates.  All fp32.
@@ -289,13 +197,11 @@ int effnet_forward(const effocr_effnet* e, const float* x, int B, float* emb, in
   return mg_finish(emb, B, EF_D, l2, status, s);
 }
 
-hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
-
 }  // namespace
 }  // namespace effocr
 
 EFFNET_API int effocr_effnet_abi_version(void) { return EFFOCR_EFFNET_ABI_VERSION; }
-EFFNET_API const char* effocr_effnet_last_error(void) { return effocr::g_effnet_err.c_str(); }
+EFFNET_API const char* effocr_effnet_last_error(void) { return g_err.c_str(); }
 
 EFFNET_API int effocr_effnet_create(const char* arch, int img_size, int precision, effocr_effnet_t** out) {
   if (!arch || !out) return fail(EFFOCR_EFFNET_EINVAL, "effnet_create: NULL argument");
@@ -308,7 +214,7 @@ EFFNET_API int effocr_effnet_create(const char* arch, int img_size, int precisio
     return fail(EFFOCR_EFFNET_EUNSUPPORTED, "effnet_create: unsupported architecture '" + a + "' (efficientnet_b0, tf_efficientnet_b0)");
   if (img_size < 32 || img_size > 224 || img_size % 32) return fail(EFFOCR_EFFNET_EINVAL, "effnet_create: img_size must be a multiple of 32 in [32, 224]");
   std::unique_ptr<effocr_effnet> e(new effocr_effnet());
-  e->img = img_size; e->prec = precision; e->tf = tf;
+  e->img = img_size; e->prec = precision; e->D = EF_D; e->tf = tf;
   build_effnet(e.get());
   *out = e.release();
   return EFFOCR_EFFNET_OK;
@@ -317,41 +223,17 @@ EFFNET_API int effocr_effnet_create(const char* arch, int img_size, int precisio
 EFFNET_API void effocr_effnet_destroy(effocr_effnet_t* enc) { delete enc; }
 EFFNET_API int effocr_effnet_embed_dim(const effocr_effnet_t* enc) { return enc ? EF_D : 0; }
 EFFNET_API int effocr_effnet_num_params(const effocr_effnet_t* enc) { return enc ? (int)enc->params.size() : 0; }
-EFFNET_API const char* effocr_effnet_param_name(const effocr_effnet_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return nullptr;
-  return enc->params[i].name.c_str();
-}
-EFFNET_API int64_t effocr_effnet_param_numel(const effocr_effnet_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return -1;
-  return enc->params[i].numel;
-}
+EFFNET_API const char* effocr_effnet_param_name(const effocr_effnet_t* enc, int i) { return enc_param_name(enc, i); }
+EFFNET_API int64_t effocr_effnet_param_numel(const effocr_effnet_t* enc, int i) { return enc_param_numel(enc, i); }
 
 EFFNET_API int effocr_effnet_set_param(effocr_effnet_t* enc, const char* name, const float* host, int64_t numel) {
-  if (!enc || !name || !host) return fail(EFFOCR_EFFNET_EINVAL, "effnet_set_param: NULL argument");
-  auto it = enc->index.find(name);
-  if (it == enc->index.end()) return fail(EFFOCR_EFFNET_EINVAL, std::string("effnet_set_param: unknown parameter '") + name + "'");
-  Param& p = enc->params[it->second];
-  if (p.numel != numel)
-    return fail(EFFOCR_EFFNET_EINVAL, std::string("effnet_set_param: '") + name + "' expects " + std::to_string(p.numel) + " elements, got " +
-                                          std::to_string(numel));
-  p.data.assign(host, host + numel);
-  p.set = true;
-  return EFFOCR_EFFNET_OK;
+  return enc_set_param("effnet", enc, name, host, numel);
 }
 
 EFFNET_API size_t effocr_effnet_weights_bytes(const effocr_effnet_t* enc) { return enc ? enc->wbytes : 0; }
 
 EFFNET_API int effocr_effnet_upload(effocr_effnet_t* enc, void* weights_dev, size_t bytes) {
-  if (!enc || !weights_dev) return fail(EFFOCR_EFFNET_EINVAL, "effnet_upload: NULL argument");
-  if (bytes < enc->wbytes) return fail(EFFOCR_EFFNET_EWORKSPACE, "effnet_upload: weight buffer too small");
-  for (const Param& p : enc->params)
-    if (!p.set) return fail(EFFOCR_EFFNET_ESTATE, "effnet_upload: parameter '" + p.name + "' was never set");
-  std::vector<char> blob(enc->wbytes, 0);
-  pack_effnet(enc, blob);
-  const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
-  if (er != hipSuccess) return fail(EFFOCR_EFFNET_EHIP, std::string("effnet_upload: hipMemcpy: ") + hipGetErrorString(er));
-  enc->wdev = static_cast<const char*>(weights_dev);
-  return EFFOCR_EFFNET_OK;
+  return enc_upload("effnet", enc, weights_dev, bytes, pack_effnet);
 }
 
 EFFNET_API size_t effocr_effnet_workspace_bytes(const effocr_effnet_t* enc, int batch) {
@@ -360,48 +242,26 @@ EFFNET_API size_t effocr_effnet_workspace_bytes(const effocr_effnet_t* enc, int 
 }
 
 EFFNET_API int effocr_effnet_set_chunk(effocr_effnet_t* enc, int crops_per_chunk) {
-  if (!enc || crops_per_chunk < 0) return fail(EFFOCR_EFFNET_EINVAL, "effnet_set_chunk: bad argument");
-  if (crops_per_chunk > EF_CHUNK_LIMIT) return fail(EFFOCR_EFFNET_EINVAL, "effnet_set_chunk: at most 65535 crops per sub-batch");
-  enc->chunk = crops_per_chunk;
-  return EFFOCR_EFFNET_OK;
+  if (enc && crops_per_chunk > EF_CHUNK_LIMIT) return fail(EFFOCR_EFFNET_EINVAL, "effnet_set_chunk: at most 65535 crops per sub-batch");
+  return enc_set_chunk("effnet", enc, crops_per_chunk);
 }
 
 EFFNET_API int effocr_effnet_forward(effocr_effnet_t* enc, const void* x_dev, int x_dtype, int batch, float* emb_dev, int l2_normalize,
                                      void* workspace_dev, size_t workspace_bytes, void* stream) {
+  // the crop type is checked before an empty batch returns, behind the two checks that come before it in every family
   if (!enc) return fail(EFFOCR_EFFNET_EINVAL, "effnet_forward: NULL encoder");
   if (batch < 0) return fail(EFFOCR_EFFNET_EINVAL, "effnet_forward: negative batch");
   if (x_dtype < 0 || x_dtype > 2) return fail(EFFOCR_EFFNET_EINVAL, "effnet_forward: unknown crop type");
   if (x_dtype != PREC_FP32) return fail(EFFOCR_EFFNET_EUNSUPPORTED, "effnet_forward: 16-bit crops are not supported (the stem is an fp32 convolution)");
-  if (batch == 0) return EFFOCR_EFFNET_OK;
-  if (!x_dev || !emb_dev || !workspace_dev) return fail(EFFOCR_EFFNET_EINVAL, "effnet_forward: NULL device pointer");
-  if (!enc->wdev) return fail(EFFOCR_EFFNET_ESTATE, "effnet_forward: weights were not uploaded");
-  if (workspace_bytes < effocr_effnet_workspace_bytes(enc, batch)) return fail(EFFOCR_EFFNET_EWORKSPACE, "effnet_forward: workspace too small");
-  const int chunk = effnet_chunk(enc, batch);
-  char* ws = static_cast<char*>(workspace_dev);
-  const float* x = static_cast<const float*>(x_dev);
-  const size_t img_elems = (size_t)3 * enc->img * enc->img;
-  // every kernel computes a crop from that crop's data alone: the embeddings are bit-identical for every chunk setting
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    const int cb = std::min(chunk, batch - b0);
-    const int rc = effnet_forward(enc, x + (size_t)b0 * img_elems, cb, emb_dev + (size_t)b0 * EF_D, l2_normalize, ws, S(stream));
-    if (rc) return rc;
-  }
-  return EFFOCR_EFFNET_OK;
+  const int rc = enc_forward_args("effnet", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_effnet_workspace_bytes(enc, batch));
+  if (rc || batch == 0) return rc;
+  return enc_forward_chunks(enc, static_cast<const float*>(x_dev), batch, effnet_chunk(enc, batch), emb_dev, [&](const float* x, int crops, float* emb) {
+    return effnet_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
+  });
 }
 
-EFFNET_API int effocr_effnet_check_status(const effocr_effnet_t* enc, const void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_EFFNET_EINVAL, "effnet_check_status: NULL argument");
-  int st = 0;
-  hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // EfWs::status = offset 0
-  if (er == hipSuccess) er = hipStreamSynchronize(S(stream));
-  if (er == hipSuccess && st != 0) er = hipMemsetAsync(const_cast<void*>(workspace_dev), 0, sizeof(int), S(stream));   // read-and-clear
-  if (er != hipSuccess) return fail(EFFOCR_EFFNET_EHIP, std::string("effnet_check_status: ") + hipGetErrorString(er));
-  if (st != 0)
-    return fail(EFFOCR_EFFNET_EOVERFLOW, enc->prec == PREC_FP16
-                    ? "forward: non-finite embedding — an f16 operand overflowed (an activation beyond 65504) or the input was not finite; use "
-                      "precision bf16 or fp32 for this checkpoint"
-                    : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
-  return EFFOCR_EFFNET_OK;
+EFFNET_API int effocr_effnet_check_status(const effocr_effnet_t* enc, const void* workspace_dev, void* stream) {   // EfWs::status = offset 0
+  return enc_check_status("effnet", enc, workspace_dev, stream, MBCONV_FP16_OVERFLOW);
 }
 
 EFFNET_API int effocr_effnet_reset_status(const effocr_effnet_t* enc, void* workspace_dev, void* stream) {

@@ -2,57 +2,24 @@
 // parameter table in timm's state-dict order, host-side BN folding and packing, sub-batched forward orchestration) and the library's own
 // error state.  The kernels are mnv3g.hip's.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_mnv3.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "mbconv_pack.hpp"
 #include "mnv3g.hpp"
 
-#include <math.h>
-#include <string.h>
-#include <algorithm>
-#include <map>
 #include <memory>
-#include <string>
-#include <vector>
 
 #define MNV3_API extern "C" __attribute__((visibility("default")))
 
 namespace effocr {
-
-// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
-static thread_local std::string g_mnv3_err;
-void set_error(const std::string& msg) { g_mnv3_err = msg; }
-int fail(int code, const std::string& msg) { g_mnv3_err = msg; return code; }
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return EFFOCR_OK;
-}
-
 namespace {
 
 // sub-batches: as many crops as keep the workspace under MG_WS_BUDGET, at most MG_MAX_CHUNK
 constexpr size_t MG_WS_BUDGET = (size_t)512 << 20;
 constexpr int MG_MAX_CHUNK = 256;
 
-struct Param { std::string name; int64_t numel; std::vector<float> data; bool set; };
-struct ConvOff { size_t w = 0, b = 0; };
 enum { BLK_DS = 0, BLK_IR = 1, BLK_CN = 2 };
 // one block of the table: geometry and blob offsets (pw = expand, dw = depthwise, ser / see = squeeze-excite reduce / expand, pwl = project
 // — for a ds block its conv_pw, for the cn block its conv)
 struct Block { std::string key; int type, cin, mid, cout, k, stride, se, hs, res; ConvOff pw, dw, ser, see, pwl; };
-
-struct Alloc {
-  size_t off = 0;
-  size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
-
-uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                            // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
 
 // timm layers/helpers.py make_divisible(v, 8, round_limit=0.9)
 int make_divisible(double v) {
@@ -87,38 +54,14 @@ const DefRow DEF_LARGE[] = {
 
 using namespace effocr;
 
-struct effocr_mnv3 {
-  int img = 224, prec = PREC_FP16, D = 0, chunk = 0;
+struct effocr_mnv3 : EncoderCore {
   int stem_c = 16;
-  std::vector<Param> params;
-  std::map<std::string, int> index;
   std::vector<Block> blocks;
   ConvOff stem, head;
-  size_t wbytes = 0;
-  const char* wdev = nullptr;
 };
 
 namespace effocr {
 namespace {
-
-void add_param(effocr_mnv3* e, const std::string& name, int64_t numel) {
-  e->index[name] = (int)e->params.size();
-  e->params.push_back(Param{name, numel, {}, false});
-}
-void add_bn(effocr_mnv3* e, const std::string& p, int c) {
-  add_param(e, p + ".weight", c); add_param(e, p + ".bias", c);
-  add_param(e, p + ".running_mean", c); add_param(e, p + ".running_var", c);
-}
-void add_se(effocr_mnv3* e, const std::string& p, int c, int r) {
-  add_param(e, p + ".se.conv_reduce.weight", (int64_t)r * c); add_param(e, p + ".se.conv_reduce.bias", r);
-  add_param(e, p + ".se.conv_expand.weight", (int64_t)c * r); add_param(e, p + ".se.conv_expand.bias", c);
-}
-const std::vector<float>& P(const effocr_mnv3* e, const std::string& n) { return e->params[e->index.at(n)].data; }
-
-size_t pw_bytes(const effocr_mnv3* e, int N, int K) {
-  if (e->prec == PREC_FP32) return (size_t)N * K * 4;
-  return (size_t)align_up(N, 16) * align_up(K, 16) * 2;       // zero-padded to whole 16 x 16 MFMA tiles
-}
 
 // The block list the way timm's _efficientnet_builder derives it, the parameter table in timm's state-dict order (a module's own
 // parameters, then its children's) and the blob layout.
@@ -145,103 +88,69 @@ void build_mnv3(effocr_mnv3* e, bool large, double mult) {
   }
   e->D = large ? 1280 : 1024;                                 // conv_head: not scaled by the multiplier
 
-  add_param(e, "conv_stem.weight", (int64_t)e->stem_c * 27);
-  add_bn(e, "bn1", e->stem_c);
+  e->add_param("conv_stem.weight", (int64_t)e->stem_c * 27);
+  e->add_bn("bn1", e->stem_c);
   for (const Block& b : e->blocks) {
     const std::string& p = b.key;
     if (b.type == BLK_DS) {
-      add_param(e, p + ".conv_dw.weight", (int64_t)b.cin * b.k * b.k); add_bn(e, p + ".bn1", b.cin);
+      e->add_param(p + ".conv_dw.weight", (int64_t)b.cin * b.k * b.k); e->add_bn(p + ".bn1", b.cin);
       if (b.se) add_se(e, p, b.cin, b.se);
-      add_param(e, p + ".conv_pw.weight", (int64_t)b.cout * b.cin); add_bn(e, p + ".bn2", b.cout);
+      e->add_param(p + ".conv_pw.weight", (int64_t)b.cout * b.cin); e->add_bn(p + ".bn2", b.cout);
     } else if (b.type == BLK_IR) {
-      add_param(e, p + ".conv_pw.weight", (int64_t)b.mid * b.cin); add_bn(e, p + ".bn1", b.mid);
-      add_param(e, p + ".conv_dw.weight", (int64_t)b.mid * b.k * b.k); add_bn(e, p + ".bn2", b.mid);
+      e->add_param(p + ".conv_pw.weight", (int64_t)b.mid * b.cin); e->add_bn(p + ".bn1", b.mid);
+      e->add_param(p + ".conv_dw.weight", (int64_t)b.mid * b.k * b.k); e->add_bn(p + ".bn2", b.mid);
       if (b.se) add_se(e, p, b.mid, b.se);
-      add_param(e, p + ".conv_pwl.weight", (int64_t)b.cout * b.mid); add_bn(e, p + ".bn3", b.cout);
+      e->add_param(p + ".conv_pwl.weight", (int64_t)b.cout * b.mid); e->add_bn(p + ".bn3", b.cout);
     } else {
-      add_param(e, p + ".conv.weight", (int64_t)b.cout * b.cin); add_bn(e, p + ".bn1", b.cout);
+      e->add_param(p + ".conv.weight", (int64_t)b.cout * b.cin); e->add_bn(p + ".bn1", b.cout);
     }
   }
-  add_param(e, "conv_head.weight", (int64_t)e->D * cin);
-  add_param(e, "conv_head.bias", e->D);
+  e->add_param("conv_head.weight", (int64_t)e->D * cin);
+  e->add_param("conv_head.bias", e->D);
 
   Alloc a;
   e->stem.w = a.take((size_t)27 * e->stem_c * 4); e->stem.b = a.take((size_t)e->stem_c * 4);
   for (Block& b : e->blocks) {
-    if (b.type == BLK_IR) { b.pw.w = a.take(pw_bytes(e, b.mid, b.cin)); b.pw.b = a.take((size_t)b.mid * 4); }
+    if (b.type == BLK_IR) { b.pw.w = a.take(pw_bytes(e->prec, b.mid, b.cin)); b.pw.b = a.take((size_t)b.mid * 4); }
     if (b.type != BLK_CN) { b.dw.w = a.take((size_t)b.k * b.k * b.mid * 4); b.dw.b = a.take((size_t)b.mid * 4); }
     if (b.se) {
       b.ser.w = a.take((size_t)b.se * b.mid * 4); b.ser.b = a.take((size_t)b.se * 4);
       b.see.w = a.take((size_t)b.mid * b.se * 4); b.see.b = a.take((size_t)b.mid * 4);
     }
     const int K = b.type == BLK_CN ? b.cin : b.mid;
-    b.pwl.w = a.take(pw_bytes(e, b.cout, K)); b.pwl.b = a.take((size_t)b.cout * 4);
+    b.pwl.w = a.take(pw_bytes(e->prec, b.cout, K)); b.pwl.b = a.take((size_t)b.cout * 4);
   }
-  e->head.w = a.take(pw_bytes(e, e->D, cin)); e->head.b = a.take((size_t)e->D * 4);
+  e->head.w = a.take(pw_bytes(e->prec, e->D, cin)); e->head.b = a.take((size_t)e->D * 4);
   e->wbytes = a.off;
 }
-
-// pointwise weight [N][K] fp32 -> the blob: fp32 as it is, else rounded once to the operand type inside a zeroed [N16][K16] frame
-void put_pw(const effocr_mnv3* e, std::vector<char>& blob, size_t off, const float* w, int N, int K) {
-  if (e->prec == PREC_FP32) { memcpy(blob.data() + off, w, (size_t)N * K * 4); return; }
-  const int Kp = (int)align_up(K, 16);
-  uint16_t* d = reinterpret_cast<uint16_t*>(blob.data() + off);   // (the blob starts zeroed)
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) d[(size_t)n * Kp + k] = e->prec == PREC_BF16 ? f32_to_bf16(w[(size_t)n * K + k]) : f32_to_f16(w[(size_t)n * K + k]);
-}
-void put_f32(std::vector<char>& blob, size_t off, const float* v, size_t n) { memcpy(blob.data() + off, v, n * 4); }
 
 // Every BatchNorm (eval, eps 1e-5) folded into the conv in front of it in fp32, as libeffocr_hip.so does for mobilenetv3_small_050:
 // w' = w g / sqrt(v + eps), b' = beta - m g / sqrt(v + eps).  Depthwise and stem weights tap-major; SE convs fp32 as they are.
 void pack_mnv3(const effocr_mnv3* e, std::vector<char>& blob) {
-  std::vector<float> wf, bf;
-  auto fold = [&](const std::string& w, const std::string& bn) {
-    const auto& W = P(e, w);
-    const auto& g = P(e, bn + ".weight"); const auto& be = P(e, bn + ".bias");
-    const auto& m = P(e, bn + ".running_mean"); const auto& v = P(e, bn + ".running_var");
-    const size_t C = g.size(), per = W.size() / C;
-    wf.resize(W.size()); bf.resize(C);
-    for (size_t c = 0; c < C; ++c) {
-      const float sc = g[c] / sqrtf(v[c] + 1e-5f);
-      for (size_t k = 0; k < per; ++k) wf[c * per + k] = W[c * per + k] * sc;
-      bf[c] = be[c] - m[c] * sc;
-    }
-  };
-  auto pw = [&](const ConvOff& c, const std::string& w, const std::string& bn, int N, int K) {
-    fold(w, bn); put_pw(e, blob, c.w, wf.data(), N, K); put_f32(blob, c.b, bf.data(), bf.size());
-  };
-  auto tapmajor = [&](const ConvOff& c, const std::string& w, const std::string& bn, int C, int taps) {
-    fold(w, bn);
-    float* d = reinterpret_cast<float*>(blob.data() + c.w);
-    for (int ch = 0; ch < C; ++ch)
-      for (int t = 0; t < taps; ++t) d[(size_t)t * C + ch] = wf[(size_t)ch * taps + t];
-    put_f32(blob, c.b, bf.data(), bf.size());
-  };
+  BnFolder f{e, blob, 1e-5f};
   auto plain = [&](const ConvOff& c, const std::string& p) {
-    const auto& w = P(e, p + ".weight"); const auto& b = P(e, p + ".bias");
+    const auto& w = e->P(p + ".weight"); const auto& b = e->P(p + ".bias");
     put_f32(blob, c.w, w.data(), w.size()); put_f32(blob, c.b, b.data(), b.size());
   };
-  tapmajor(e->stem, "conv_stem.weight", "bn1", e->stem_c, 27);           // [ci][ky][kx] taps
+  f.tapmajor(e->stem, "conv_stem.weight", "bn1", e->stem_c, 27);           // [ci][ky][kx] taps
   for (const Block& b : e->blocks) {
     const std::string& p = b.key;
     if (b.type == BLK_DS) {
-      tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn1", b.cin, b.k * b.k);
-      pw(b.pwl, p + ".conv_pw.weight", p + ".bn2", b.cout, b.cin);
+      f.tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn1", b.cin, b.k * b.k);
+      f.pw(b.pwl, p + ".conv_pw.weight", p + ".bn2", b.cout, b.cin);
     } else if (b.type == BLK_IR) {
-      pw(b.pw, p + ".conv_pw.weight", p + ".bn1", b.mid, b.cin);
-      tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn2", b.mid, b.k * b.k);
-      pw(b.pwl, p + ".conv_pwl.weight", p + ".bn3", b.cout, b.mid);
+      f.pw(b.pw, p + ".conv_pw.weight", p + ".bn1", b.mid, b.cin);
+      f.tapmajor(b.dw, p + ".conv_dw.weight", p + ".bn2", b.mid, b.k * b.k);
+      f.pw(b.pwl, p + ".conv_pwl.weight", p + ".bn3", b.cout, b.mid);
     } else {
-      pw(b.pwl, p + ".conv.weight", p + ".bn1", b.cout, b.cin);
+      f.pw(b.pwl, p + ".conv.weight", p + ".bn1", b.cout, b.cin);
     }
     if (b.se) { plain(b.ser, p + ".se.conv_reduce"); plain(b.see, p + ".se.conv_expand"); }
   }
   const Block& last = e->blocks.back();
-  put_pw(e, blob, e->head.w, P(e, "conv_head.weight").data(), e->D, last.cout);
-  put_f32(blob, e->head.b, P(e, "conv_head.bias").data(), e->D);
+  put_pw(e->prec, blob, e->head.w, e->P("conv_head.weight").data(), e->D, last.cout);
+  put_f32(blob, e->head.b, e->P("conv_head.bias").data(), e->D);
 }
-
-int out_size(int H, int stride) { return (H - 1) / stride + 1; }           // k x k, pad k / 2
 
 // Workspace of one sub-batch of B crops: the status word; two block input / output maps (ping-pong); the expansion (at the block's input
 // resolution; the ConvBnAct's output too); the depthwise output; the squeeze-excite gates; the pooled features.  All fp32.
@@ -316,13 +225,11 @@ int mnv3_forward(const effocr_mnv3* e, const float* x, int B, float* emb, int l2
   return mg_finish(emb, B, e->D, l2, status, s);
 }
 
-hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
-
 }  // namespace
 }  // namespace effocr
 
 MNV3_API int effocr_mnv3_abi_version(void) { return EFFOCR_MNV3_ABI_VERSION; }
-MNV3_API const char* effocr_mnv3_last_error(void) { return effocr::g_mnv3_err.c_str(); }
+MNV3_API const char* effocr_mnv3_last_error(void) { return g_err.c_str(); }
 
 MNV3_API int effocr_mnv3_create(const char* arch, int img_size, int precision, effocr_mnv3_t** out) {
   if (!arch || !out) return fail(EFFOCR_MNV3_EINVAL, "mnv3_create: NULL argument");
@@ -348,41 +255,17 @@ MNV3_API int effocr_mnv3_create(const char* arch, int img_size, int precision, e
 MNV3_API void effocr_mnv3_destroy(effocr_mnv3_t* enc) { delete enc; }
 MNV3_API int effocr_mnv3_embed_dim(const effocr_mnv3_t* enc) { return enc ? enc->D : 0; }
 MNV3_API int effocr_mnv3_num_params(const effocr_mnv3_t* enc) { return enc ? (int)enc->params.size() : 0; }
-MNV3_API const char* effocr_mnv3_param_name(const effocr_mnv3_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return nullptr;
-  return enc->params[i].name.c_str();
-}
-MNV3_API int64_t effocr_mnv3_param_numel(const effocr_mnv3_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return -1;
-  return enc->params[i].numel;
-}
+MNV3_API const char* effocr_mnv3_param_name(const effocr_mnv3_t* enc, int i) { return enc_param_name(enc, i); }
+MNV3_API int64_t effocr_mnv3_param_numel(const effocr_mnv3_t* enc, int i) { return enc_param_numel(enc, i); }
 
 MNV3_API int effocr_mnv3_set_param(effocr_mnv3_t* enc, const char* name, const float* host, int64_t numel) {
-  if (!enc || !name || !host) return fail(EFFOCR_MNV3_EINVAL, "mnv3_set_param: NULL argument");
-  auto it = enc->index.find(name);
-  if (it == enc->index.end()) return fail(EFFOCR_MNV3_EINVAL, std::string("mnv3_set_param: unknown parameter '") + name + "'");
-  Param& p = enc->params[it->second];
-  if (p.numel != numel)
-    return fail(EFFOCR_MNV3_EINVAL, std::string("mnv3_set_param: '") + name + "' expects " + std::to_string(p.numel) + " elements, got " +
-                                        std::to_string(numel));
-  p.data.assign(host, host + numel);
-  p.set = true;
-  return EFFOCR_MNV3_OK;
+  return enc_set_param("mnv3", enc, name, host, numel);
 }
 
 MNV3_API size_t effocr_mnv3_weights_bytes(const effocr_mnv3_t* enc) { return enc ? enc->wbytes : 0; }
 
 MNV3_API int effocr_mnv3_upload(effocr_mnv3_t* enc, void* weights_dev, size_t bytes) {
-  if (!enc || !weights_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_upload: NULL argument");
-  if (bytes < enc->wbytes) return fail(EFFOCR_MNV3_EWORKSPACE, "mnv3_upload: weight buffer too small");
-  for (const Param& p : enc->params)
-    if (!p.set) return fail(EFFOCR_MNV3_ESTATE, "mnv3_upload: parameter '" + p.name + "' was never set");
-  std::vector<char> blob(enc->wbytes, 0);
-  pack_mnv3(enc, blob);
-  const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
-  if (er != hipSuccess) return fail(EFFOCR_MNV3_EHIP, std::string("mnv3_upload: hipMemcpy: ") + hipGetErrorString(er));
-  enc->wdev = static_cast<const char*>(weights_dev);
-  return EFFOCR_MNV3_OK;
+  return enc_upload("mnv3", enc, weights_dev, bytes, pack_mnv3);
 }
 
 MNV3_API size_t effocr_mnv3_workspace_bytes(const effocr_mnv3_t* enc, int batch) {
@@ -390,43 +273,17 @@ MNV3_API size_t effocr_mnv3_workspace_bytes(const effocr_mnv3_t* enc, int batch)
   return mnv3_ws(enc, mnv3_chunk(enc, batch)).total;
 }
 
-MNV3_API int effocr_mnv3_set_chunk(effocr_mnv3_t* enc, int crops_per_chunk) {
-  if (!enc || crops_per_chunk < 0) return fail(EFFOCR_MNV3_EINVAL, "mnv3_set_chunk: bad argument");
-  enc->chunk = crops_per_chunk;
-  return EFFOCR_MNV3_OK;
-}
+MNV3_API int effocr_mnv3_set_chunk(effocr_mnv3_t* enc, int crops_per_chunk) { return enc_set_chunk("mnv3", enc, crops_per_chunk); }
 
 MNV3_API int effocr_mnv3_forward(effocr_mnv3_t* enc, const float* x_dev, int batch, float* emb_dev, int l2_normalize, void* workspace_dev,
                                  size_t workspace_bytes, void* stream) {
-  if (!enc) return fail(EFFOCR_MNV3_EINVAL, "mnv3_forward: NULL encoder");
-  if (batch < 0) return fail(EFFOCR_MNV3_EINVAL, "mnv3_forward: negative batch");
-  if (batch == 0) return EFFOCR_MNV3_OK;
-  if (!x_dev || !emb_dev || !workspace_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_forward: NULL device pointer");
-  if (!enc->wdev) return fail(EFFOCR_MNV3_ESTATE, "mnv3_forward: weights were not uploaded");
-  if (workspace_bytes < effocr_mnv3_workspace_bytes(enc, batch)) return fail(EFFOCR_MNV3_EWORKSPACE, "mnv3_forward: workspace too small");
-  const int chunk = mnv3_chunk(enc, batch);
-  char* ws = static_cast<char*>(workspace_dev);
-  const size_t img_elems = (size_t)3 * enc->img * enc->img;
-  // every kernel computes a crop from that crop's data alone: the embeddings are bit-identical for every chunk setting
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    const int cb = std::min(chunk, batch - b0);
-    const int rc = mnv3_forward(enc, x_dev + (size_t)b0 * img_elems, cb, emb_dev + (size_t)b0 * enc->D, l2_normalize, ws, S(stream));
-    if (rc) return rc;
-  }
-  return EFFOCR_MNV3_OK;
+  const int rc = enc_forward_args("mnv3", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_mnv3_workspace_bytes(enc, batch));
+  if (rc || batch == 0) return rc;
+  return enc_forward_chunks(enc, x_dev, batch, mnv3_chunk(enc, batch), emb_dev, [&](const float* x, int crops, float* emb) {
+    return mnv3_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
+  });
 }
 
-MNV3_API int effocr_mnv3_check_status(const effocr_mnv3_t* enc, const void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_check_status: NULL argument");
-  int st = 0;
-  hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // MgWs::status = offset 0
-  if (er == hipSuccess) er = hipStreamSynchronize(S(stream));
-  if (er == hipSuccess && st != 0) er = hipMemsetAsync(const_cast<void*>(workspace_dev), 0, sizeof(int), S(stream));   // read-and-clear
-  if (er != hipSuccess) return fail(EFFOCR_MNV3_EHIP, std::string("mnv3_check_status: ") + hipGetErrorString(er));
-  if (st != 0)
-    return fail(EFFOCR_MNV3_EOVERFLOW, enc->prec == PREC_FP16
-                    ? "forward: non-finite embedding — an f16 operand overflowed (an activation beyond 65504) or the input was not finite; use "
-                      "precision bf16 or fp32 for this checkpoint"
-                    : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
-  return EFFOCR_MNV3_OK;
+MNV3_API int effocr_mnv3_check_status(const effocr_mnv3_t* enc, const void* workspace_dev, void* stream) {   // MgWs::status = offset 0
+  return enc_check_status("mnv3", enc, workspace_dev, stream, MBCONV_FP16_OVERFLOW);
 }

@@ -3,43 +3,15 @@
 // fp32 mode runs the exact-fp32 convolution pipeline of resnet.hip, which this library compiles a second time with hidden visibility, with
 // its split-K turned off.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_resnet.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "enc_core.hpp"
 #include "resnet16.hpp"
 
 #include <math.h>
-#include <string.h>
-#include <algorithm>
-#include <map>
 #include <memory>
-#include <string>
-#include <vector>
 
 #define RESNET_API extern "C" __attribute__((visibility("default")))
 
 namespace effocr {
-
-// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
-static thread_local std::string g_resnet_err;
-void set_error(const std::string& msg) { g_resnet_err = msg; }
-int fail(int code, const std::string& msg) { g_resnet_err = msg; return code; }
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return EFFOCR_OK;
-}
-int device_cus() {
-  static int cache[64] = {0};                            // benign race: every thread computes the same value
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cache[dev] == 0) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cache[dev] = v;
-  }
-  return cache[dev];
-}
-
 namespace {
 
 // sub-batches: as many crops as keep the workspace under RN_WS_BUDGET (1 GB < 1 GiB), at most RN_MAX_CHUNK
@@ -47,59 +19,30 @@ constexpr size_t RN_WS_BUDGET = (size_t)1000 << 20;
 constexpr int RN_MAX_CHUNK = 256;
 constexpr int RN_STEM_K32 = 160;   // fp32 stem im2col columns (resnet.hip's im2col_conv1: 147 taps padded to 5 K-stages of 32)
 
-struct Param { std::string name; int64_t numel; std::vector<float> data; bool set; };
 // one convolution + its BatchNorm: timm key prefixes, geometry and blob offsets (weights [cout][kpad], bias [cout] fp32)
 struct Conv { std::string w, bn; int cin, cout, k, stride, pad, kpad; size_t w_off, b_off; };
 // one residual block: convs[c0 ..] = conv1, conv2 (, conv3) (, downsample)
 struct Block { int c0, nconv, stride; bool down; };
-
-struct Alloc {
-  size_t off = 0;
-  size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
-
-uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                            // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
 
 }  // namespace
 }  // namespace effocr
 
 using namespace effocr;
 
-struct effocr_resnet {
-  int img = 224, prec = PREC_FP16, D = 0, chunk = 0;
+struct effocr_resnet : EncoderCore {
   bool bottleneck = false;
-  std::vector<Param> params;
-  std::map<std::string, int> index;
   std::vector<Conv> convs;          // conv1 (stem), then the blocks' convolutions in forward order
   std::vector<Block> blocks;
-  size_t wbytes = 0;
-  const char* wdev = nullptr;
 };
 
 namespace effocr {
 namespace {
 
-void add_param(effocr_resnet* e, const std::string& name, int64_t numel) {
-  e->index[name] = (int)e->params.size();
-  e->params.push_back(Param{name, numel, {}, false});
-}
-void add_bn(effocr_resnet* e, const std::string& p, int c) {
-  add_param(e, p + ".weight", c); add_param(e, p + ".bias", c);
-  add_param(e, p + ".running_mean", c); add_param(e, p + ".running_var", c);
-}
 void add_conv(effocr_resnet* e, const std::string& w, const std::string& bn, int cin, int cout, int k, int stride, int pad) {
-  add_param(e, w, (int64_t)cout * cin * k * k);
-  add_bn(e, bn, cout);
+  e->add_param(w, (int64_t)cout * cin * k * k);
+  e->add_bn(bn, cout);
   e->convs.push_back(Conv{w, bn, cin, cout, k, stride, pad, k * k * cin, 0, 0});
 }
-
-const std::vector<float>& P(const effocr_resnet* e, const std::string& n) { return e->params[e->index.at(n)].data; }
 
 // timm resnet34 (BasicBlock) / resnet50 (Bottleneck): depths 3-4-6-3, widths 64-128-256-512 (x4 expansion for the bottleneck),
 // 7x7/2 stem + 3x3/2 max pool, the stride on the 3x3 conv (the bottleneck's conv2), a 1x1 stride-s conv + BN shortcut, BN eps 1e-5.
@@ -143,9 +86,9 @@ void build_resnet(effocr_resnet* e) {
 // from torch [Cout,Cin,KH,KW] to [Cout][KH][KW][Cin] (Cin fastest), zero-padded to kpad columns, then rounded once to the operand type.
 void pack_resnet(const effocr_resnet* e, std::vector<char>& blob) {
   for (const Conv& c : e->convs) {
-    const auto& w = P(e, c.w);
-    const auto& g = P(e, c.bn + ".weight"); const auto& bt = P(e, c.bn + ".bias");
-    const auto& mu = P(e, c.bn + ".running_mean"); const auto& var = P(e, c.bn + ".running_var");
+    const auto& w = e->P(c.w);
+    const auto& g = e->P(c.bn + ".weight"); const auto& bt = e->P(c.bn + ".bias");
+    const auto& mu = e->P(c.bn + ".running_mean"); const auto& var = e->P(c.bn + ".running_var");
     std::vector<float> wd((size_t)c.cout * c.kpad, 0.f);
     float* bd = reinterpret_cast<float*>(blob.data() + c.b_off);
     for (int co = 0; co < c.cout; ++co) {
@@ -158,9 +101,7 @@ void pack_resnet(const effocr_resnet* e, std::vector<char>& blob) {
             wd[(size_t)co * c.kpad + (ky * c.k + kx) * c.cin + cc] = (float)((double)v * sc);
           }
     }
-    if (e->prec == PREC_FP32) { memcpy(blob.data() + c.w_off, wd.data(), wd.size() * 4); continue; }
-    uint16_t* d = reinterpret_cast<uint16_t*>(blob.data() + c.w_off);
-    for (size_t i = 0; i < wd.size(); ++i) d[i] = e->prec == PREC_BF16 ? f32_to_bf16(wd[i]) : f32_to_f16(wd[i]);
+    put_op(blob, c.w_off, wd.data(), wd.size(), e->prec);
   }
 }
 
@@ -255,13 +196,11 @@ int resnet_forward(const effocr_resnet* e, const float* x, int B, float* emb, in
   return rn_avgpool(e->prec, buf[cur], emb, B, H * H, e->D, l2, status, s);
 }
 
-hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
-
 }  // namespace
 }  // namespace effocr
 
 RESNET_API int effocr_resnet_abi_version(void) { return EFFOCR_RESNET_ABI_VERSION; }
-RESNET_API const char* effocr_resnet_last_error(void) { return effocr::g_resnet_err.c_str(); }
+RESNET_API const char* effocr_resnet_last_error(void) { return g_err.c_str(); }
 
 RESNET_API int effocr_resnet_create(const char* arch, int img_size, int precision, effocr_resnet_t** out) {
   if (!arch || !out) return fail(EFFOCR_RESNET_EINVAL, "resnet_create: NULL argument");
@@ -280,41 +219,17 @@ RESNET_API int effocr_resnet_create(const char* arch, int img_size, int precisio
 RESNET_API void effocr_resnet_destroy(effocr_resnet_t* enc) { delete enc; }
 RESNET_API int effocr_resnet_embed_dim(const effocr_resnet_t* enc) { return enc ? enc->D : 0; }
 RESNET_API int effocr_resnet_num_params(const effocr_resnet_t* enc) { return enc ? (int)enc->params.size() : 0; }
-RESNET_API const char* effocr_resnet_param_name(const effocr_resnet_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return nullptr;
-  return enc->params[i].name.c_str();
-}
-RESNET_API int64_t effocr_resnet_param_numel(const effocr_resnet_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return -1;
-  return enc->params[i].numel;
-}
+RESNET_API const char* effocr_resnet_param_name(const effocr_resnet_t* enc, int i) { return enc_param_name(enc, i); }
+RESNET_API int64_t effocr_resnet_param_numel(const effocr_resnet_t* enc, int i) { return enc_param_numel(enc, i); }
 
 RESNET_API int effocr_resnet_set_param(effocr_resnet_t* enc, const char* name, const float* host, int64_t numel) {
-  if (!enc || !name || !host) return fail(EFFOCR_RESNET_EINVAL, "resnet_set_param: NULL argument");
-  auto it = enc->index.find(name);
-  if (it == enc->index.end()) return fail(EFFOCR_RESNET_EINVAL, std::string("resnet_set_param: unknown parameter '") + name + "'");
-  Param& p = enc->params[it->second];
-  if (p.numel != numel)
-    return fail(EFFOCR_RESNET_EINVAL, std::string("resnet_set_param: '") + name + "' expects " + std::to_string(p.numel) +
-                                          " elements, got " + std::to_string(numel));
-  p.data.assign(host, host + numel);
-  p.set = true;
-  return EFFOCR_RESNET_OK;
+  return enc_set_param("resnet", enc, name, host, numel);
 }
 
 RESNET_API size_t effocr_resnet_weights_bytes(const effocr_resnet_t* enc) { return enc ? enc->wbytes : 0; }
 
 RESNET_API int effocr_resnet_upload(effocr_resnet_t* enc, void* weights_dev, size_t bytes) {
-  if (!enc || !weights_dev) return fail(EFFOCR_RESNET_EINVAL, "resnet_upload: NULL argument");
-  if (bytes < enc->wbytes) return fail(EFFOCR_RESNET_EWORKSPACE, "resnet_upload: weight buffer too small");
-  for (const Param& p : enc->params)
-    if (!p.set) return fail(EFFOCR_RESNET_ESTATE, "resnet_upload: parameter '" + p.name + "' was never set");
-  std::vector<char> blob(enc->wbytes, 0);
-  pack_resnet(enc, blob);
-  const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
-  if (er != hipSuccess) return fail(EFFOCR_RESNET_EHIP, std::string("resnet_upload: hipMemcpy: ") + hipGetErrorString(er));
-  enc->wdev = static_cast<const char*>(weights_dev);
-  return EFFOCR_RESNET_OK;
+  return enc_upload("resnet", enc, weights_dev, bytes, pack_resnet);
 }
 
 RESNET_API size_t effocr_resnet_workspace_bytes(const effocr_resnet_t* enc, int batch) {
@@ -322,46 +237,23 @@ RESNET_API size_t effocr_resnet_workspace_bytes(const effocr_resnet_t* enc, int 
   return resnet_ws(enc, resnet_chunk(enc, batch)).total;
 }
 
-RESNET_API int effocr_resnet_set_chunk(effocr_resnet_t* enc, int crops_per_chunk) {
-  if (!enc || crops_per_chunk < 0) return fail(EFFOCR_RESNET_EINVAL, "resnet_set_chunk: bad argument");
-  enc->chunk = crops_per_chunk;
-  return EFFOCR_RESNET_OK;
-}
+RESNET_API int effocr_resnet_set_chunk(effocr_resnet_t* enc, int crops_per_chunk) { return enc_set_chunk("resnet", enc, crops_per_chunk); }
 
 RESNET_API int effocr_resnet_forward(effocr_resnet_t* enc, const float* x_dev, int batch, float* emb_dev, int l2_normalize,
                                      void* workspace_dev, size_t workspace_bytes, void* stream) {
-  if (!enc) return fail(EFFOCR_RESNET_EINVAL, "resnet_forward: NULL encoder");
-  if (batch < 0) return fail(EFFOCR_RESNET_EINVAL, "resnet_forward: negative batch");
-  if (batch == 0) return EFFOCR_RESNET_OK;
-  if (!x_dev || !emb_dev || !workspace_dev) return fail(EFFOCR_RESNET_EINVAL, "resnet_forward: NULL device pointer");
-  if (!enc->wdev) return fail(EFFOCR_RESNET_ESTATE, "resnet_forward: weights were not uploaded");
-  if (workspace_bytes < effocr_resnet_workspace_bytes(enc, batch)) return fail(EFFOCR_RESNET_EWORKSPACE, "resnet_forward: workspace too small");
+  const int rc = enc_forward_args("resnet", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_resnet_workspace_bytes(enc, batch));
+  if (rc || batch == 0) return rc;
   const int chunk = resnet_chunk(enc, batch);
   const int64_t s2 = (int64_t)(enc->img / 2) * (enc->img / 2);
   if ((int64_t)chunk * s2 * enc->convs[0].kpad >= (int64_t)1 << 31)
     return fail(EFFOCR_RESNET_EUNSUPPORTED, "resnet_forward: chunk too large for 32-bit activation indices (effocr_resnet_set_chunk)");
-  char* ws = static_cast<char*>(workspace_dev);
-  const size_t img_elems = (size_t)3 * enc->img * enc->img;
-  // every kernel reads and writes its own crops' pixels only: the embeddings are bit-identical for every chunk setting
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    const int cb = std::min(chunk, batch - b0);
-    const int rc = resnet_forward(enc, x_dev + (size_t)b0 * img_elems, cb, emb_dev + (size_t)b0 * enc->D, l2_normalize, ws, S(stream));
-    if (rc) return rc;
-  }
-  return EFFOCR_RESNET_OK;
+  return enc_forward_chunks(enc, x_dev, batch, chunk, emb_dev, [&](const float* x, int crops, float* emb) {
+    return resnet_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
+  });
 }
 
-RESNET_API int effocr_resnet_check_status(const effocr_resnet_t* enc, const void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_RESNET_EINVAL, "resnet_check_status: NULL argument");
-  int st = 0;
-  hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // RnWs::status = offset 0
-  if (er == hipSuccess) er = hipStreamSynchronize(S(stream));
-  if (er == hipSuccess && st != 0) er = hipMemsetAsync(const_cast<void*>(workspace_dev), 0, sizeof(int), S(stream));   // read-and-clear
-  if (er != hipSuccess) return fail(EFFOCR_RESNET_EHIP, std::string("resnet_check_status: ") + hipGetErrorString(er));
-  if (st != 0)
-    return fail(EFFOCR_RESNET_EOVERFLOW, enc->prec == PREC_FP16
-                    ? "forward: non-finite embedding — an f16 activation overflowed (beyond 65504) or the input was not finite; use "
-                      "precision bf16 or fp32 for this checkpoint"
-                    : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
-  return EFFOCR_RESNET_OK;
+RESNET_API int effocr_resnet_check_status(const effocr_resnet_t* enc, const void* workspace_dev, void* stream) {   // RnWs::status = offset 0
+  return enc_check_status("resnet", enc, workspace_dev, stream,
+                          "forward: non-finite embedding — an f16 activation overflowed (beyond 65504) or the input was not finite; use "
+                          "precision bf16 or fp32 for this checkpoint");
 }

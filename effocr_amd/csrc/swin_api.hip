@@ -2,42 +2,14 @@
 // orchestration over swin.hip's kernels and the GEMMs of gemm.hip / gemm2.hip, which this library compiles a second time with hidden
 // visibility) and the library's own error state.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_swin.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "enc_core.hpp"
 #include "swin.hpp"
 
-#include <string.h>
-#include <algorithm>
-#include <map>
 #include <memory>
-#include <string>
-#include <vector>
 
 #define SWIN_API extern "C" __attribute__((visibility("default")))
 
 namespace effocr {
-
-// the error plumbing common.hpp declares, for the kernels linked into this library (its own thread-local message)
-static thread_local std::string g_swin_err;
-void set_error(const std::string& msg) { g_swin_err = msg; }
-int fail(int code, const std::string& msg) { g_swin_err = msg; return code; }
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(EFFOCR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return EFFOCR_OK;
-}
-int device_cus() {
-  static int cache[64] = {0};                            // benign race: every thread computes the same value
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cache[dev] == 0) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cache[dev] = v;
-  }
-  return cache[dev];
-}
-
 namespace {
 
 constexpr float SWIN_EPS = 1e-5f;                        // nn.LayerNorm's default: every LayerNorm of timm's Swin
@@ -46,56 +18,31 @@ constexpr int SWIN_WS = 7, SWIN_SHIFT = 3;
 constexpr size_t SWIN_WS_BUDGET = (size_t)1000 << 20;
 constexpr int SWIN_MAX_CHUNK = 192;
 
-struct Param { std::string name; int64_t numel; std::vector<float> data; bool set; };
 struct BlockOff { size_t ln1w, ln1b, qkvw, qkvb, table, projw, projb, ln2w, ln2b, fc1w, fc1b, fc2w, fc2b; int shift; };
 struct StageOff { int C, Cp, H, depth; size_t mlnw, mlnb, redw, redb; std::vector<BlockOff> blocks; };
-
-struct Alloc {
-  size_t off = 0;
-  size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
-
-uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                            // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
 
 }  // namespace
 }  // namespace effocr
 
 using namespace effocr;
 
-struct effocr_swin {
-  int img = 224, prec = PREC_FP16, D = 768, chunk = 0;
-  std::vector<Param> params;
-  std::map<std::string, int> index;
+struct effocr_swin : EncoderCore {
   std::vector<StageOff> st;
-  size_t stemw = 0, stemb = 0, stemlnw = 0, stemlnb = 0, normw = 0, normb = 0, wbytes = 0;
-  const char* wdev = nullptr;
+  size_t stemw = 0, stemb = 0, stemlnw = 0, stemlnb = 0, normw = 0, normb = 0;
 };
 
 namespace effocr {
 namespace {
-
-void add_param(effocr_swin* e, const std::string& name, int64_t numel) {
-  e->index[name] = (int)e->params.size();
-  e->params.push_back(Param{name, numel, {}, false});
-}
-
-const std::vector<float>& P(const effocr_swin* e, const std::string& n) { return e->params[e->index.at(n)].data; }
 
 // swin_tiny_patch4_window7_224: depths 2-2-6-2, widths 96-192-384-768, head dim 32, window 7, mlp ratio 4.  Key names: timm >= 0.9.
 void build_swin(effocr_swin* e) {
   static const int depths[4] = {2, 2, 6, 2}, widths[4] = {96, 192, 384, 768};
   const size_t es = prec_esize(e->prec);
   Alloc a;
-  add_param(e, "patch_embed.proj.weight", (int64_t)widths[0] * 48);
-  add_param(e, "patch_embed.proj.bias", widths[0]);
-  add_param(e, "patch_embed.norm.weight", widths[0]);
-  add_param(e, "patch_embed.norm.bias", widths[0]);
+  e->add_param("patch_embed.proj.weight", (int64_t)widths[0] * 48);
+  e->add_param("patch_embed.proj.bias", widths[0]);
+  e->add_param("patch_embed.norm.weight", widths[0]);
+  e->add_param("patch_embed.norm.bias", widths[0]);
   e->stemw = a.take((size_t)48 * 128 * 4);
   e->stemb = a.take(128 * 4); e->stemlnw = a.take(128 * 4); e->stemlnb = a.take(128 * 4);
   e->st.resize(4);
@@ -108,22 +55,22 @@ void build_swin(effocr_swin* e) {
     const std::string p = "layers." + std::to_string(i) + ".";
     if (i > 0) {
       const int Cv = widths[i - 1];
-      add_param(e, p + "downsample.norm.weight", 4 * Cv);
-      add_param(e, p + "downsample.norm.bias", 4 * Cv);
-      add_param(e, p + "downsample.reduction.weight", (int64_t)C * 4 * Cv);
+      e->add_param(p + "downsample.norm.weight", 4 * Cv);
+      e->add_param(p + "downsample.norm.bias", 4 * Cv);
+      e->add_param(p + "downsample.reduction.weight", (int64_t)C * 4 * Cv);
       s.mlnw = a.take((size_t)4 * Cv * 4); s.mlnb = a.take((size_t)4 * Cv * 4);
       s.redw = a.take((size_t)Cp * 4 * Cv * es); s.redb = a.take((size_t)Cp * 4);      // reduction has no bias: a zero vector
     }
     s.blocks.resize(depths[i]);
     for (int j = 0; j < depths[i]; ++j) {
       const std::string q = p + "blocks." + std::to_string(j) + ".";
-      add_param(e, q + "norm1.weight", C); add_param(e, q + "norm1.bias", C);
-      add_param(e, q + "attn.relative_position_bias_table", (int64_t)(2 * SWIN_WS - 1) * (2 * SWIN_WS - 1) * heads);
-      add_param(e, q + "attn.qkv.weight", (int64_t)3 * C * C); add_param(e, q + "attn.qkv.bias", 3 * C);
-      add_param(e, q + "attn.proj.weight", (int64_t)C * C); add_param(e, q + "attn.proj.bias", C);
-      add_param(e, q + "norm2.weight", C); add_param(e, q + "norm2.bias", C);
-      add_param(e, q + "mlp.fc1.weight", (int64_t)4 * C * C); add_param(e, q + "mlp.fc1.bias", 4 * C);
-      add_param(e, q + "mlp.fc2.weight", (int64_t)4 * C * C); add_param(e, q + "mlp.fc2.bias", C);
+      e->add_param(q + "norm1.weight", C); e->add_param(q + "norm1.bias", C);
+      e->add_param(q + "attn.relative_position_bias_table", (int64_t)(2 * SWIN_WS - 1) * (2 * SWIN_WS - 1) * heads);
+      e->add_param(q + "attn.qkv.weight", (int64_t)3 * C * C); e->add_param(q + "attn.qkv.bias", 3 * C);
+      e->add_param(q + "attn.proj.weight", (int64_t)C * C); e->add_param(q + "attn.proj.bias", C);
+      e->add_param(q + "norm2.weight", C); e->add_param(q + "norm2.bias", C);
+      e->add_param(q + "mlp.fc1.weight", (int64_t)4 * C * C); e->add_param(q + "mlp.fc1.bias", 4 * C);
+      e->add_param(q + "mlp.fc2.weight", (int64_t)4 * C * C); e->add_param(q + "mlp.fc2.bias", C);
       BlockOff& L = s.blocks[j];
       L.shift = (j % 2 == 1 && H > SWIN_WS) ? SWIN_SHIFT : 0;       // timm: no shift when the map is one window
       L.ln1w = a.take((size_t)Cp * 4); L.ln1b = a.take((size_t)Cp * 4);
@@ -135,18 +82,11 @@ void build_swin(effocr_swin* e) {
       L.fc2w = a.take((size_t)Cp * 4 * C * es); L.fc2b = a.take((size_t)Cp * 4);
     }
   }
-  add_param(e, "norm.weight", widths[3]); add_param(e, "norm.bias", widths[3]);
+  e->add_param("norm.weight", widths[3]); e->add_param("norm.bias", widths[3]);
   e->normw = a.take((size_t)e->st[3].Cp * 4); e->normb = a.take((size_t)e->st[3].Cp * 4);
   e->wbytes = a.off;
 }
 
-void put_f32(std::vector<char>& blob, size_t off, const float* src, size_t n) { memcpy(blob.data() + off, src, n * 4); }
-void put_op(std::vector<char>& blob, size_t off, const float* src, size_t n, int prec) {
-  if (prec == PREC_FP32) { memcpy(blob.data() + off, src, n * 4); return; }
-  uint16_t* d = reinterpret_cast<uint16_t*>(blob.data() + off);
-  if (prec == PREC_BF16) for (size_t i = 0; i < n; ++i) d[i] = f32_to_bf16(src[i]);
-  else for (size_t i = 0; i < n; ++i) d[i] = f32_to_f16(src[i]);
-}
 // [rows][cols] -> [rows_p][cols_p] zero-padded, rows mapped by rmap (row r of the source lands on row rmap(r))
 template <typename F>
 std::vector<float> pad2(const std::vector<float>& w, int rows, int cols, int rows_p, int cols_p, F rmap) {
@@ -159,10 +99,10 @@ std::vector<float> pad2(const std::vector<float>& w, int rows, int cols, int row
 // proj [C][C] -> [Cp][Cp]; fc1 [4C][C] -> [4C][Cp]; fc2 [C][4C] -> [Cp][4C]; reduction [C][4Cv] -> [Cp][4Cv]; patch_embed conv tap-major
 // [48][128]; bias tables as they are ([169][heads] fp32).  Zero pad rows / columns keep the residual's pad channels exactly 0.
 void pack_swin(const effocr_swin* e, std::vector<char>& blob) {
-  auto padf = [&](size_t off, const std::string& n) { const auto& v = P(e, n); put_f32(blob, off, v.data(), v.size()); };
+  auto padf = [&](size_t off, const std::string& n) { const auto& v = e->P(n); put_f32(blob, off, v.data(), v.size()); };
   const int prec = e->prec;
   {
-    const auto& w = P(e, "patch_embed.proj.weight");
+    const auto& w = e->P("patch_embed.proj.weight");
     const int C0 = e->st[0].C;
     float* d = reinterpret_cast<float*>(blob.data() + e->stemw);
     for (int c = 0; c < C0; ++c)
@@ -176,7 +116,7 @@ void pack_swin(const effocr_swin* e, std::vector<char>& blob) {
     if (i > 0) {
       const int Cv = e->st[i - 1].C;
       padf(s.mlnw, p + "downsample.norm.weight"); padf(s.mlnb, p + "downsample.norm.bias");
-      const auto t = pad2(P(e, p + "downsample.reduction.weight"), C, 4 * Cv, Cp, 4 * Cv, [](int r) { return r; });
+      const auto t = pad2(e->P(p + "downsample.reduction.weight"), C, 4 * Cv, Cp, 4 * Cv, [](int r) { return r; });
       put_op(blob, s.redw, t.data(), t.size(), prec);
     }
     for (int j = 0; j < s.depth; ++j) {
@@ -187,18 +127,18 @@ void pack_swin(const effocr_swin* e, std::vector<char>& blob) {
       padf(L.table, q + "attn.relative_position_bias_table");
       padf(L.projb, q + "attn.proj.bias"); padf(L.fc1b, q + "mlp.fc1.bias"); padf(L.fc2b, q + "mlp.fc2.bias");
       auto qmap = [C, Cp](int r) { return (r / C) * Cp + r % C; };
-      auto t = pad2(P(e, q + "attn.qkv.weight"), 3 * C, C, 3 * Cp, Cp, qmap);
+      auto t = pad2(e->P(q + "attn.qkv.weight"), 3 * C, C, 3 * Cp, Cp, qmap);
       put_op(blob, L.qkvw, t.data(), t.size(), prec);
       {
-        const auto& b = P(e, q + "attn.qkv.bias");
+        const auto& b = e->P(q + "attn.qkv.bias");
         float* d = reinterpret_cast<float*>(blob.data() + L.qkvb);
         for (int r = 0; r < 3 * C; ++r) d[qmap(r)] = b[r];
       }
-      t = pad2(P(e, q + "attn.proj.weight"), C, C, Cp, Cp, [](int r) { return r; });
+      t = pad2(e->P(q + "attn.proj.weight"), C, C, Cp, Cp, [](int r) { return r; });
       put_op(blob, L.projw, t.data(), t.size(), prec);
-      t = pad2(P(e, q + "mlp.fc1.weight"), 4 * C, C, 4 * C, Cp, [](int r) { return r; });
+      t = pad2(e->P(q + "mlp.fc1.weight"), 4 * C, C, 4 * C, Cp, [](int r) { return r; });
       put_op(blob, L.fc1w, t.data(), t.size(), prec);
-      t = pad2(P(e, q + "mlp.fc2.weight"), C, 4 * C, Cp, 4 * C, [](int r) { return r; });
+      t = pad2(e->P(q + "mlp.fc2.weight"), C, 4 * C, Cp, 4 * C, [](int r) { return r; });
       put_op(blob, L.fc2w, t.data(), t.size(), prec);
     }
   }
@@ -274,13 +214,11 @@ int swin_forward(const effocr_swin* e, const float* x, int B, float* emb, int l2
   return swin_head(xs, B, last.H * last.H, last.C, last.Cp, F(e->normw), F(e->normb), SWIN_EPS, l2, emb, status, s);
 }
 
-hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
-
 }  // namespace
 }  // namespace effocr
 
 SWIN_API int effocr_swin_abi_version(void) { return EFFOCR_SWIN_ABI_VERSION; }
-SWIN_API const char* effocr_swin_last_error(void) { return effocr::g_swin_err.c_str(); }
+SWIN_API const char* effocr_swin_last_error(void) { return g_err.c_str(); }
 
 SWIN_API int effocr_swin_create(const char* arch, int img_size, int precision, effocr_swin_t** out) {
   if (!arch || !out) return fail(EFFOCR_SWIN_EINVAL, "swin_create: NULL argument");
@@ -291,7 +229,7 @@ SWIN_API int effocr_swin_create(const char* arch, int img_size, int precision, e
     return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_create: img_size must be 224 (the reference builds swin_tiny_patch4_window7_224 at "
                                           "timm's default size; other sizes change the window grid)");
   std::unique_ptr<effocr_swin> e(new effocr_swin());
-  e->img = img_size; e->prec = precision;
+  e->img = img_size; e->prec = precision; e->D = 768;
   build_swin(e.get());
   *out = e.release();
   return EFFOCR_SWIN_OK;
@@ -300,41 +238,17 @@ SWIN_API int effocr_swin_create(const char* arch, int img_size, int precision, e
 SWIN_API void effocr_swin_destroy(effocr_swin_t* enc) { delete enc; }
 SWIN_API int effocr_swin_embed_dim(const effocr_swin_t* enc) { return enc ? enc->D : 0; }
 SWIN_API int effocr_swin_num_params(const effocr_swin_t* enc) { return enc ? (int)enc->params.size() : 0; }
-SWIN_API const char* effocr_swin_param_name(const effocr_swin_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return nullptr;
-  return enc->params[i].name.c_str();
-}
-SWIN_API int64_t effocr_swin_param_numel(const effocr_swin_t* enc, int i) {
-  if (!enc || i < 0 || i >= (int)enc->params.size()) return -1;
-  return enc->params[i].numel;
-}
+SWIN_API const char* effocr_swin_param_name(const effocr_swin_t* enc, int i) { return enc_param_name(enc, i); }
+SWIN_API int64_t effocr_swin_param_numel(const effocr_swin_t* enc, int i) { return enc_param_numel(enc, i); }
 
 SWIN_API int effocr_swin_set_param(effocr_swin_t* enc, const char* name, const float* host, int64_t numel) {
-  if (!enc || !name || !host) return fail(EFFOCR_SWIN_EINVAL, "swin_set_param: NULL argument");
-  auto it = enc->index.find(name);
-  if (it == enc->index.end()) return fail(EFFOCR_SWIN_EINVAL, std::string("swin_set_param: unknown parameter '") + name + "'");
-  Param& p = enc->params[it->second];
-  if (p.numel != numel)
-    return fail(EFFOCR_SWIN_EINVAL, std::string("swin_set_param: '") + name + "' expects " + std::to_string(p.numel) + " elements, got " +
-                                        std::to_string(numel));
-  p.data.assign(host, host + numel);
-  p.set = true;
-  return EFFOCR_SWIN_OK;
+  return enc_set_param("swin", enc, name, host, numel);
 }
 
 SWIN_API size_t effocr_swin_weights_bytes(const effocr_swin_t* enc) { return enc ? enc->wbytes : 0; }
 
 SWIN_API int effocr_swin_upload(effocr_swin_t* enc, void* weights_dev, size_t bytes) {
-  if (!enc || !weights_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_upload: NULL argument");
-  if (bytes < enc->wbytes) return fail(EFFOCR_SWIN_EWORKSPACE, "swin_upload: weight buffer too small");
-  for (const Param& p : enc->params)
-    if (!p.set) return fail(EFFOCR_SWIN_ESTATE, "swin_upload: parameter '" + p.name + "' was never set");
-  std::vector<char> blob(enc->wbytes, 0);
-  pack_swin(enc, blob);
-  const hipError_t er = hipMemcpy(weights_dev, blob.data(), enc->wbytes, hipMemcpyHostToDevice);
-  if (er != hipSuccess) return fail(EFFOCR_SWIN_EHIP, std::string("swin_upload: hipMemcpy: ") + hipGetErrorString(er));
-  enc->wdev = static_cast<const char*>(weights_dev);
-  return EFFOCR_SWIN_OK;
+  return enc_upload("swin", enc, weights_dev, bytes, pack_swin);
 }
 
 SWIN_API size_t effocr_swin_workspace_bytes(const effocr_swin_t* enc, int batch) {
@@ -342,46 +256,23 @@ SWIN_API size_t effocr_swin_workspace_bytes(const effocr_swin_t* enc, int batch)
   return swin_ws(enc, swin_chunk(enc, batch)).total;
 }
 
-SWIN_API int effocr_swin_set_chunk(effocr_swin_t* enc, int crops_per_chunk) {
-  if (!enc || crops_per_chunk < 0) return fail(EFFOCR_SWIN_EINVAL, "swin_set_chunk: bad argument");
-  enc->chunk = crops_per_chunk;
-  return EFFOCR_SWIN_OK;
-}
+SWIN_API int effocr_swin_set_chunk(effocr_swin_t* enc, int crops_per_chunk) { return enc_set_chunk("swin", enc, crops_per_chunk); }
 
 SWIN_API int effocr_swin_forward(effocr_swin_t* enc, const float* x_dev, int batch, float* emb_dev, int l2_normalize, void* workspace_dev,
                                  size_t workspace_bytes, void* stream) {
-  if (!enc) return fail(EFFOCR_SWIN_EINVAL, "swin_forward: NULL encoder");
-  if (batch < 0) return fail(EFFOCR_SWIN_EINVAL, "swin_forward: negative batch");
-  if (batch == 0) return EFFOCR_SWIN_OK;
-  if (!x_dev || !emb_dev || !workspace_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_forward: NULL device pointer");
-  if (!enc->wdev) return fail(EFFOCR_SWIN_ESTATE, "swin_forward: weights were not uploaded");
-  if (workspace_bytes < effocr_swin_workspace_bytes(enc, batch)) return fail(EFFOCR_SWIN_EWORKSPACE, "swin_forward: workspace too small");
+  const int rc = enc_forward_args("swin", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_swin_workspace_bytes(enc, batch));
+  if (rc || batch == 0) return rc;
   const int chunk = swin_chunk(enc, batch);
   const int64_t tok0 = (int64_t)(enc->img / 4) * (enc->img / 4);
   if ((int64_t)chunk * tok0 * std::max(3 * enc->st[0].Cp, 4 * enc->st[0].C) >= (int64_t)1 << 31)
     return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_forward: chunk too large for 32-bit GEMM indices (effocr_swin_set_chunk)");
-  char* ws = static_cast<char*>(workspace_dev);
-  const size_t img_elems = (size_t)3 * enc->img * enc->img;
-  // every kernel reads and writes its own crops' rows only: the embeddings are bit-identical for every chunk setting
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    const int cb = std::min(chunk, batch - b0);
-    const int rc = swin_forward(enc, x_dev + (size_t)b0 * img_elems, cb, emb_dev + (size_t)b0 * enc->D, l2_normalize, ws, S(stream));
-    if (rc) return rc;
-  }
-  return EFFOCR_SWIN_OK;
+  return enc_forward_chunks(enc, x_dev, batch, chunk, emb_dev, [&](const float* x, int crops, float* emb) {
+    return swin_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
+  });
 }
 
-SWIN_API int effocr_swin_check_status(const effocr_swin_t* enc, const void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_check_status: NULL argument");
-  int st = 0;
-  hipError_t er = hipMemcpyAsync(&st, workspace_dev, sizeof(int), hipMemcpyDeviceToHost, S(stream));   // SwinWs::status = offset 0
-  if (er == hipSuccess) er = hipStreamSynchronize(S(stream));
-  if (er == hipSuccess && st != 0) er = hipMemsetAsync(const_cast<void*>(workspace_dev), 0, sizeof(int), S(stream));   // read-and-clear
-  if (er != hipSuccess) return fail(EFFOCR_SWIN_EHIP, std::string("swin_check_status: ") + hipGetErrorString(er));
-  if (st != 0)
-    return fail(EFFOCR_SWIN_EOVERFLOW, enc->prec == PREC_FP16
-                    ? "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
-                      "input was not finite; use precision bf16 or fp32 for this checkpoint"
-                    : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
-  return EFFOCR_SWIN_OK;
+SWIN_API int effocr_swin_check_status(const effocr_swin_t* enc, const void* workspace_dev, void* stream) {   // SwinWs::status = offset 0
+  return enc_check_status("swin", enc, workspace_dev, stream,
+                          "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
+                          "input was not finite; use precision bf16 or fp32 for this checkpoint");
 }

@@ -35,30 +35,37 @@ class HipEncoder:
     covers only the enqueue; two threads forwarding on different streams must not share activation buffers)."""
 
     def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
+        self._create(_lib.lib, "effocr_encoder", lambda rc, what: _lib.check(rc, what, self._L), arch, state_dict, img_size, precision, device)
+        # calls of 192..640 crops run as 2-4 concurrent sub-batches of ~128 crops on side streams (ViT-S, 16-bit modes; forward_split below)
+        self.split_streams = True
+
+    def _create(self, load, prefix, check, arch, state_dict, img_size, precision, device):
+        """Create the handle, set every parameter and upload the packed weights through the entry points ``<prefix>_*`` of the library
+        ``load()`` returns; ``check(rc, what)`` raises with that library's last_error."""
         if precision not in _lib.PREC:
             raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
         self.device = _lib.require_gpu(device)
         self.arch, self.img_size, self.precision = arch, int(img_size), precision
-        self._L = _lib.lib()
+        self._L = load()
         self._lock = threading.Lock()
         self._h = ctypes.c_void_p()
-        _lib.check(self._L.effocr_encoder_create(arch.encode(), self.img_size, _lib.PREC[precision],
-                                                 ctypes.byref(self._h)), "effocr_encoder_create", self._L)
-        self.embed_dim = int(self._L.effocr_encoder_embed_dim(self._h))
+
+        def fn(name):
+            return getattr(self._L, f"{prefix}_{name}")
+        check(fn("create")(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)), f"{prefix}_create")
+        self.embed_dim = int(fn("embed_dim")(self._h))
         sd = W.strip_prefix(state_dict)
         W.check_state_dict(arch, sd, self.img_size)
-        for i in range(self._L.effocr_encoder_num_params(self._h)):
-            name = self._L.effocr_encoder_param_name(self._h, i).decode()
+        for i in range(fn("num_params")(self._h)):
+            name = fn("param_name")(self._h, i).decode()
             t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            _lib.check(self._L.effocr_encoder_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()),
-                       f"effocr_encoder_set_param({name})", self._L)
-        nbytes = int(self._L.effocr_encoder_weights_bytes(self._h))
+            check(fn("set_param")(self._h, name.encode(), _lib.ptr(t), t.numel()), f"{prefix}_set_param({name})")
+        nbytes = int(fn("weights_bytes")(self._h))
         with torch.cuda.device(self.device):
             self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self._L.effocr_encoder_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_encoder_upload", self._L)
+            check(fn("upload")(self._h, _lib.ptr(self._wblob), nbytes), f"{prefix}_upload")
         self._ws = {}
-        # calls of 192..640 crops run as 2-4 concurrent sub-batches of ~128 crops on side streams (ViT-S, 16-bit modes; forward_split below)
-        self.split_streams = True
+        self.split_streams = False
         self._side = None                    # (streams, thread pool) of the split, created on first use
         self._side_used = set()              # side streams whose workspaces may hold an unchecked status word
         self._stream_locks = {}              # stream handle -> lock held while a forward is enqueued onto that stream
@@ -270,322 +277,101 @@ class HipEncoder:
         return out
 
 
-class SwinEncoder(HipEncoder):
-    """HipEncoder's interface over libeffocr_swin.so (include/effocr_swin.h): swin_tiny_patch4_window7_224 at 224^2, fp32 crops in
-    every precision mode (the patch embedding is an fp32 conv).  Same per-stream grow-only workspaces with their sticky status word;
-    no stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
+class _FamilyEncoder(HipEncoder):
+    """HipEncoder's interface over one encoder-family library: libeffocr_<_family>.so (include/effocr_<_family>.h), bound by
+    ``_lib.<_family>_lib()`` and checked by ``_lib.<_family>_check``.  fp32 crops in every precision mode.  Same per-stream grow-only
+    workspaces with their sticky status word; no stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
+    _family = None                           # "swin": the entry points effocr_swin_*
+    _label = None                            # the name the messages use
 
     def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
-        if precision not in _lib.PREC:
-            raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
-        self.device = _lib.require_gpu(device)
-        self.arch, self.img_size, self.precision = arch, int(img_size), precision
-        self._L = _lib.swin_lib()
-        self._lock = threading.Lock()
-        self._h = ctypes.c_void_p()
-        _lib.swin_check(self._L.effocr_swin_create(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)),
-                        "effocr_swin_create")
-        self.embed_dim = int(self._L.effocr_swin_embed_dim(self._h))
-        sd = W.strip_prefix(state_dict)
-        W.check_state_dict(arch, sd, self.img_size)
-        for i in range(self._L.effocr_swin_num_params(self._h)):
-            name = self._L.effocr_swin_param_name(self._h, i).decode()
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            _lib.swin_check(self._L.effocr_swin_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()), f"effocr_swin_set_param({name})")
-        nbytes = int(self._L.effocr_swin_weights_bytes(self._h))
-        with torch.cuda.device(self.device):
-            self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.swin_check(self._L.effocr_swin_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_swin_upload")
-        self._ws = {}
-        self.split_streams = False
-        self._side = None
-        self._side_used = set()
-        self._stream_locks = {}
-        self._profiling = False
+        self._create(getattr(_lib, f"{self._family}_lib"), f"effocr_{self._family}", getattr(_lib, f"{self._family}_check"),
+                     arch, state_dict, img_size, precision, device)
+
+    def _fn(self, name):
+        return getattr(self._L, f"effocr_{self._family}_{name}")
+
+    def _call(self, name, *args):
+        """effocr_<family>_<name>(handle, *args); raises EffOCRHipError with the library's message unless it returns 0."""
+        getattr(_lib, f"{self._family}_check")(self._fn(name)(self._h, *args), f"effocr_{self._family}_{name}")
 
     def __del__(self):
         try:
             if getattr(self, "_h", None) is not None and self._h.value:
-                self._L.effocr_swin_destroy(self._h)
+                self._fn("destroy")(self._h)
                 self._h = ctypes.c_void_p()
         except Exception:
             pass
 
     def set_chunk(self, crops_per_chunk):
-        """Internal sub-batch size (0 = the library's default: a workspace under 1 GB, at most 192 crops); effocr_swin_set_chunk."""
-        _lib.swin_check(self._L.effocr_swin_set_chunk(self._h, int(crops_per_chunk)), "effocr_swin_set_chunk")
+        """Internal sub-batch size (0 = the library's default, see the class); effocr_<family>_set_chunk."""
+        self._call("set_chunk", int(crops_per_chunk))
 
     def set_option(self, name, value):
-        raise ValueError(f"the Swin encoder has no option {name!r}")
+        raise ValueError(f"the {self._label} encoder has no option {name!r}")
 
     def workspace_bytes(self, batch):
-        return int(self._L.effocr_swin_workspace_bytes(self._h, int(batch)))
+        return int(self._fn("workspace_bytes")(self._h, int(batch)))
 
     @property
     def crop_dtype(self):
         return torch.float32
 
     def _enqueue(self, x, emb, normalize, ws):
-        _lib.swin_check(self._L.effocr_swin_forward(self._h, _lib.ptr(x), x.shape[0], _lib.ptr(emb), 1 if normalize else 0, _lib.ptr(ws),
-                                                    ws.numel(), _lib.current_stream(self.device)), "effocr_swin_forward")
+        self._call("forward", _lib.ptr(x), x.shape[0], _lib.ptr(emb), 1 if normalize else 0, _lib.ptr(ws), ws.numel(),
+                   _lib.current_stream(self.device))
 
-    def check_status(self):
-        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
-        non-finite embedding (the status word is sticky; this call clears it)."""
-        with self._lock, torch.cuda.device(self.device):
-            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
-            if ws is None:
-                return
-            _lib.swin_check(self._L.effocr_swin_check_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
-                            "effocr_swin_check_status")
-
-    def profile_begin(self, only=None):
-        raise NotImplementedError("the Swin encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
-
-    def profile_collect(self):
-        raise NotImplementedError("the Swin encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
-
-
-class ResNetEncoder(HipEncoder):
-    """HipEncoder's interface over libeffocr_resnet.so (include/effocr_resnet.h): resnet34 / resnet50 at any img_size that is a positive
-    multiple of 32, fp32 crops in every precision mode (the stem's im2col reads them and rounds to the operand type).  Same per-stream
-    grow-only workspaces with their sticky status word; no stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
-
-    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
-        if precision not in _lib.PREC:
-            raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
-        self.device = _lib.require_gpu(device)
-        self.arch, self.img_size, self.precision = arch, int(img_size), precision
-        self._L = _lib.resnet_lib()
-        self._lock = threading.Lock()
-        self._h = ctypes.c_void_p()
-        _lib.resnet_check(self._L.effocr_resnet_create(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)),
-                          "effocr_resnet_create")
-        self.embed_dim = int(self._L.effocr_resnet_embed_dim(self._h))
-        sd = W.strip_prefix(state_dict)
-        W.check_state_dict(arch, sd, self.img_size)
-        for i in range(self._L.effocr_resnet_num_params(self._h)):
-            name = self._L.effocr_resnet_param_name(self._h, i).decode()
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            _lib.resnet_check(self._L.effocr_resnet_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()),
-                              f"effocr_resnet_set_param({name})")
-        nbytes = int(self._L.effocr_resnet_weights_bytes(self._h))
-        with torch.cuda.device(self.device):
-            self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.resnet_check(self._L.effocr_resnet_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_resnet_upload")
-        self._ws = {}
-        self.split_streams = False
-        self._side = None
-        self._side_used = set()
-        self._stream_locks = {}
-        self._profiling = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                self._L.effocr_resnet_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
-
-    def set_chunk(self, crops_per_chunk):
-        """Internal sub-batch size (0 = the library's default: a workspace under 1 GB, at most 256 crops); effocr_resnet_set_chunk."""
-        _lib.resnet_check(self._L.effocr_resnet_set_chunk(self._h, int(crops_per_chunk)), "effocr_resnet_set_chunk")
-
-    def set_option(self, name, value):
-        raise ValueError(f"the ResNet-34/50 encoder has no option {name!r}")
-
-    def workspace_bytes(self, batch):
-        return int(self._L.effocr_resnet_workspace_bytes(self._h, int(batch)))
-
-    @property
-    def crop_dtype(self):
-        return torch.float32
-
-    def _enqueue(self, x, emb, normalize, ws):
-        _lib.resnet_check(self._L.effocr_resnet_forward(self._h, _lib.ptr(x), x.shape[0], _lib.ptr(emb), 1 if normalize else 0,
-                                                        _lib.ptr(ws), ws.numel(), _lib.current_stream(self.device)), "effocr_resnet_forward")
-
-    def check_status(self):
-        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
-        non-finite embedding (the status word is sticky; this call clears it)."""
-        with self._lock, torch.cuda.device(self.device):
-            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
-            if ws is None:
-                return
-            _lib.resnet_check(self._L.effocr_resnet_check_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
-                              "effocr_resnet_check_status")
-
-    def profile_begin(self, only=None):
-        raise NotImplementedError("the ResNet-34/50 encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
-
-    def profile_collect(self):
-        raise NotImplementedError("the ResNet-34/50 encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
-
-
-class MobileNetV3Encoder(HipEncoder):
-    """HipEncoder's interface over libeffocr_mnv3.so (include/effocr_mnv3.h): mobilenetv3_small_075 / mobilenetv3_small_100 /
-    mobilenetv3_large_100 at any img_size that is a multiple of 32 from 32 to 224, fp32 crops in every precision mode (the stem is an fp32
-    conv).  mobilenetv3_small_050 stays on HipEncoder (libeffocr_hip.so).  Same per-stream grow-only workspaces with their sticky status
-    word; no stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
-
-    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
-        if precision not in _lib.PREC:
-            raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
-        self.device = _lib.require_gpu(device)
-        self.arch, self.img_size, self.precision = arch, int(img_size), precision
-        self._L = _lib.mnv3_lib()
-        self._lock = threading.Lock()
-        self._h = ctypes.c_void_p()
-        _lib.mnv3_check(self._L.effocr_mnv3_create(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)),
-                          "effocr_mnv3_create")
-        self.embed_dim = int(self._L.effocr_mnv3_embed_dim(self._h))
-        sd = W.strip_prefix(state_dict)
-        W.check_state_dict(arch, sd, self.img_size)
-        for i in range(self._L.effocr_mnv3_num_params(self._h)):
-            name = self._L.effocr_mnv3_param_name(self._h, i).decode()
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            _lib.mnv3_check(self._L.effocr_mnv3_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()),
-                              f"effocr_mnv3_set_param({name})")
-        nbytes = int(self._L.effocr_mnv3_weights_bytes(self._h))
-        with torch.cuda.device(self.device):
-            self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.mnv3_check(self._L.effocr_mnv3_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_mnv3_upload")
-        self._ws = {}
-        self.split_streams = False
-        self._side = None
-        self._side_used = set()
-        self._stream_locks = {}
-        self._profiling = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                self._L.effocr_mnv3_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
-
-    def set_chunk(self, crops_per_chunk):
-        """Internal sub-batch size (0 = the library's default: a workspace under 512 MiB, at most 256 crops); effocr_mnv3_set_chunk."""
-        _lib.mnv3_check(self._L.effocr_mnv3_set_chunk(self._h, int(crops_per_chunk)), "effocr_mnv3_set_chunk")
-
-    def set_option(self, name, value):
-        raise ValueError(f"the MobileNetV3 family encoder has no option {name!r}")
-
-    def workspace_bytes(self, batch):
-        return int(self._L.effocr_mnv3_workspace_bytes(self._h, int(batch)))
-
-    @property
-    def crop_dtype(self):
-        return torch.float32
-
-    def _enqueue(self, x, emb, normalize, ws):
-        _lib.mnv3_check(self._L.effocr_mnv3_forward(self._h, _lib.ptr(x), x.shape[0], _lib.ptr(emb), 1 if normalize else 0,
-                                                        _lib.ptr(ws), ws.numel(), _lib.current_stream(self.device)), "effocr_mnv3_forward")
-
-    def check_status(self):
-        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
-        non-finite embedding (the status word is sticky; this call clears it)."""
-        with self._lock, torch.cuda.device(self.device):
-            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
-            if ws is None:
-                return
-            _lib.mnv3_check(self._L.effocr_mnv3_check_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
-                              "effocr_mnv3_check_status")
-
-    def profile_begin(self, only=None):
-        raise NotImplementedError("the MobileNetV3 family encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
-
-    def profile_collect(self):
-        raise NotImplementedError("the MobileNetV3 family encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
-
-
-class EfficientNetEncoder(HipEncoder):
-    """HipEncoder's interface over libeffocr_effnet.so (include/effocr_effnet.h): efficientnet_b0 / tf_efficientnet_b0 at any img_size that
-    is a multiple of 32 from 32 to 224, fp32 crops in every precision mode (the stem is an fp32 conv).  The two names share keys and
-    shapes: ``arch`` alone selects the BN eps and the padding.  Same per-stream grow-only workspaces with their sticky status word; no
-    stream split and no in-library profiler (rocprofv3 gives the kernel breakdown)."""
-
-    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
-        if precision not in _lib.PREC:
-            raise ValueError(f"precision must be one of {sorted(_lib.PREC)}, got {precision!r}")
-        self.device = _lib.require_gpu(device)
-        self.arch, self.img_size, self.precision = arch, int(img_size), precision
-        self._L = _lib.effnet_lib()
-        self._lock = threading.Lock()
-        self._h = ctypes.c_void_p()
-        _lib.effnet_check(self._L.effocr_effnet_create(arch.encode(), self.img_size, _lib.PREC[precision], ctypes.byref(self._h)),
-                          "effocr_effnet_create")
-        self.embed_dim = int(self._L.effocr_effnet_embed_dim(self._h))
-        sd = W.strip_prefix(state_dict)
-        W.check_state_dict(arch, sd, self.img_size)
-        for i in range(self._L.effocr_effnet_num_params(self._h)):
-            name = self._L.effocr_effnet_param_name(self._h, i).decode()
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            _lib.effnet_check(self._L.effocr_effnet_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()),
-                              f"effocr_effnet_set_param({name})")
-        nbytes = int(self._L.effocr_effnet_weights_bytes(self._h))
-        with torch.cuda.device(self.device):
-            self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.effnet_check(self._L.effocr_effnet_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_effnet_upload")
-        self._ws = {}
-        self.split_streams = False
-        self._side = None
-        self._side_used = set()
-        self._stream_locks = {}
-        self._profiling = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                self._L.effocr_effnet_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
-
-    def set_chunk(self, crops_per_chunk):
-        """Internal sub-batch size (0 = the library's default: a workspace within 512 MiB, at most 256 crops); effocr_effnet_set_chunk."""
-        _lib.effnet_check(self._L.effocr_effnet_set_chunk(self._h, int(crops_per_chunk)), "effocr_effnet_set_chunk")
-
-    def set_option(self, name, value):
-        raise ValueError(f"the EfficientNet encoder has no option {name!r}")
-
-    def workspace_bytes(self, batch):
-        return int(self._L.effocr_effnet_workspace_bytes(self._h, int(batch)))
-
-    @property
-    def crop_dtype(self):
-        return torch.float32
-
-    def _enqueue(self, x, emb, normalize, ws):
-        _lib.effnet_check(self._L.effocr_effnet_forward(self._h, _lib.ptr(x), _lib.PREC["fp32"], x.shape[0], _lib.ptr(emb),
-                                                        1 if normalize else 0, _lib.ptr(ws), ws.numel(),
-                                                        _lib.current_stream(self.device)), "effocr_effnet_forward")
-
-    def check_status(self):
-        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
-        non-finite embedding (the status word is sticky; this call clears it)."""
-        with self._lock, torch.cuda.device(self.device):
-            ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
-            if ws is None:
-                return
-            _lib.effnet_check(self._L.effocr_effnet_check_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
-                              "effocr_effnet_check_status")
-
-    def reset_status(self):
-        """Clear the current stream's status word without reading it (asynchronous)."""
+    def _status_call(self, name):
+        """effocr_<family>_<name> on the status word of the current stream's workspace, if that stream has one."""
         with self._lock, torch.cuda.device(self.device):
             ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
             if ws is not None:
-                _lib.effnet_check(self._L.effocr_effnet_reset_status(self._h, _lib.ptr(ws), _lib.current_stream(self.device)),
-                                  "effocr_effnet_reset_status")
+                self._call(name, _lib.ptr(ws), _lib.current_stream(self.device))
+
+    def check_status(self):
+        """Synchronise the current stream and raise EffOCRHipError (code -6) if any forward on it since the previous check produced a
+        non-finite embedding (the status word is sticky; this call clears it)."""
+        self._status_call("check_status")
 
     def profile_begin(self, only=None):
-        raise NotImplementedError("the EfficientNet encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+        raise NotImplementedError(f"the {self._label} encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
 
     def profile_collect(self):
-        raise NotImplementedError("the EfficientNet encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+        raise NotImplementedError(f"the {self._label} encoder has no in-library profiler: use rocprofv3 --kernel-trace --stats")
+
+
+class SwinEncoder(_FamilyEncoder):
+    """libeffocr_swin.so: swin_tiny_patch4_window7_224 at 224^2 (the patch embedding is an fp32 conv).  Default sub-batch: a workspace
+    under 1 GB, at most 192 crops."""
+    _family, _label = "swin", "Swin"
+
+
+class ResNetEncoder(_FamilyEncoder):
+    """libeffocr_resnet.so: resnet34 / resnet50 at any img_size that is a positive multiple of 32 (the stem's im2col reads the fp32
+    crops and rounds to the operand type).  Default sub-batch: a workspace under 1 GB, at most 256 crops."""
+    _family, _label = "resnet", "ResNet-34/50"
+
+
+class MobileNetV3Encoder(_FamilyEncoder):
+    """libeffocr_mnv3.so: mobilenetv3_small_075 / mobilenetv3_small_100 / mobilenetv3_large_100 at any img_size that is a multiple of 32
+    from 32 to 224 (the stem is an fp32 conv).  mobilenetv3_small_050 stays on HipEncoder (libeffocr_hip.so).  Default sub-batch: a
+    workspace under 512 MiB, at most 256 crops."""
+    _family, _label = "mnv3", "MobileNetV3 family"
+
+
+class EfficientNetEncoder(_FamilyEncoder):
+    """libeffocr_effnet.so: efficientnet_b0 / tf_efficientnet_b0 at any img_size that is a multiple of 32 from 32 to 224 (the stem is an
+    fp32 conv).  The two names share keys and shapes: ``arch`` alone selects the BN eps and the padding.  Default sub-batch: a workspace
+    within 512 MiB, at most 256 crops."""
+    _family, _label = "effnet", "EfficientNet"
+
+    def _enqueue(self, x, emb, normalize, ws):             # (the crop type after the crops)
+        self._call("forward", _lib.ptr(x), _lib.PREC["fp32"], x.shape[0], _lib.ptr(emb), 1 if normalize else 0, _lib.ptr(ws), ws.numel(),
+                   _lib.current_stream(self.device))
+
+    def reset_status(self):
+        """Clear the current stream's status word without reading it (asynchronous)."""
+        self._status_call("reset_status")
 
 
 def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
