@@ -48,6 +48,9 @@
 #ifndef QA_BARRIER_DRAIN
 #define QA_BARRIER_DRAIN 0
 #endif
+#ifndef QA_EDGE_BLOCK_MAJOR
+#define QA_EDGE_BLOCK_MAJOR 1                            // 0: every projection stage k-step-major, the hand-over behind the section's last MFMA
+#endif
 
 namespace effocr {
 namespace {
@@ -227,103 +230,207 @@ __global__ __launch_bounds__(256, 1) void qkvattn_kernel(QkvAttnArgs a) {
       QA_STAMP_AT(0)
       V8 qf[NA][4];                                      // Q^T operand fragments of the wave's tiles (k-step = 16 head dims)
       V8 f0, f1;                                         // the k-step's two W fragments (row blocks 0 / 1 of the stage)
+      // EDGE (QA_EDGE_BLOCK_MAJOR): the first and the last ring stage of a section issue their MFMAs row-block-major — row block 0's eight
+      // k-steps, then row block 1's — instead of k-step-major.  acc[*][0] is then final 16 MFMAs before the section ends and acc[*][1] stays
+      // untouched through the first 16 MFMAs of the next section, so the hand-over of either half (accumulators + bias -> 16-bit fragment ->
+      // qf / sK / sV) runs in the gaps of the other half's MFMAs instead of behind the section's last MFMA with the matrix pipe idle: the
+      // overlap of a second accumulator set with the existing 64 registers.  Every accumulator still sums its k-steps in ascending order.
+      // The miniature width (KT = 1: the first stage of a section is also its last) keeps the k-step-major order.
+      constexpr bool EDGE = QA_EDGE_BLOCK_MAJOR && KT >= 2;
+      f32x16 acc[NA][2];                                 // [tile][row block]; EDGE: row block 1 lives into the next section's first stage
+      // ---- hand-over: accumulators (+ bias) -> 16-bit operand fragments.  Registers 8m..8m+7 of row block i = fragment (i, m).
+      f32x4 hbq[2][2][2];                                // q / k bias of fragment (i, m): registers 0-3 | 4-7
+      float hbv[2];                                      // v bias of row block i (one feature per lane)
+      float hs[8];                                       // the fragment in the making (one at a time)
+      u32x4 hp;
+      auto hand_bias = [&](auto SEC_, auto I_) __attribute__((always_inline)) {
+        constexpr int sec = decltype(SEC_)::value, i = decltype(I_)::value;
+        if constexpr (sec < 2) {
+          const float* bp = sBias + sec * D + h * 64 + i * 32 + 4 * half;
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            hbq[i][m][0] = *reinterpret_cast<const f32x4*>(bp + 8 * (2 * m));
+            hbq[i][m][1] = *reinterpret_cast<const f32x4*>(bp + 8 * (2 * m + 1));
+          }
+        } else {
+          hbv[i] = sBias[2 * D + h * 64 + i * 32 + r31];
+        }
+      };
+      // one fragment in four parts (a part is what goes into ONE gap between two MFMAs): 4 adds | 4 adds | pack4 | pack4 + store.
+      // The empty asm statements pin a part's results where they are computed: the sched_barriers around a part hold the machine
+      // scheduler only, and the SLP vectoriser otherwise rebuilds the fragment's whole add / convert tree at its root, the store.
+      u32x2 hlo;
+      auto hand_part = [&](auto SEC_, auto I_, auto TT_, auto M_, auto PART_) __attribute__((always_inline)) {
+        constexpr int sec = decltype(SEC_)::value, i = decltype(I_)::value, tt = decltype(TT_)::value, m = decltype(M_)::value, part = decltype(PART_)::value;
+        if constexpr (part < 2) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if constexpr (sec < 2) hs[4 * part + j] = acc[tt][i][8 * m + 4 * part + j] + hbq[i][m][part][j];
+            else hs[4 * part + j] = acc[tt][i][8 * m + 4 * part + j] + hbv[i];
+          }
+          asm volatile("" : "+v"(hs[4 * part]), "+v"(hs[4 * part + 1]), "+v"(hs[4 * part + 2]), "+v"(hs[4 * part + 3]));
+        } else if constexpr (part == 2) {
+          hlo = pack4<E>(hs[0], hs[1], hs[2], hs[3]);
+          asm volatile("" : "+v"(hlo));
+        } else {
+          const u32x2 hi = pack4<E>(hs[4], hs[5], hs[6], hs[7]);
+          hp = u32x4{hlo[0], hlo[1], hi[0], hi[1]};
+          const int tile = 2 * w + tt;
+          // with the one-tile body for wave 3 (7 token tiles) neither body owns a dummy tile; a run-time guard here would also let the
+          // compiler sink the whole fragment's arithmetic behind its branch, out of the gaps it is sliced into
+          constexpr bool REAL = QA_ODD_TILE_WAVE && NTT == 7;
+          if constexpr (sec == 0) qf[tt][2 * i + m] = __builtin_bit_cast(V8, hp);
+          else if (REAL || tile < NTT) {
+            if constexpr (sec == 1) *reinterpret_cast<u32x4*>(sK + ((tile * 4 + 2 * i + m) * 64 + lane) * 16) = hp;
+            else *reinterpret_cast<u32x4*>(sV + (((tile * 2 + m) * 2 + i) * 64 + lane) * 16) = hp;
+          }
+        }
+      };
+      // a whole row block at once, behind its last MFMA (the k-step-major order; EDGE: only v's second half, which no projection stage follows)
+      auto hand_block = [&](auto SEC_, auto I_) __attribute__((always_inline)) {
+        hand_bias(SEC_, I_);
+        qa_for<0, NT>([&](auto TT_) {
+          qa_for<0, 2>([&](auto M_) {
+            qa_for<0, 4>([&](auto PART_) { hand_part(SEC_, I_, TT_, M_, PART_); });
+          });
+        });
+      };
       qa_for<0, 3>([&](auto SEC_) {
         constexpr int sec = decltype(SEC_)::value;       // 0 q, 1 k, 2 v
-        f32x16 acc[NA][2];
+        if constexpr (!EDGE) {                           // (EDGE: a row block starts from zero at its first MFMA of the section)
 #pragma unroll
-        for (int tt = 0; tt < NA; ++tt)
+          for (int tt = 0; tt < NA; ++tt)
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tt][i][r] = 0.f;
+              for (int r = 0; r < 16; ++r) acc[tt][i][r] = 0.f;
+        }
         qa_for<0, KT>([&](auto KT_) {
           constexpr int kt = decltype(KT_)::value;
           constexpr int sl = sec * KT + kt;              // stage within the head
           constexpr int ft = NSH - 1 - sl;               // LAST: stages that follow in the whole stream
+          constexpr bool BM = EDGE && (kt == 0 || kt == KT - 1);   // this stage is row-block-major
+          constexpr bool NEXT_BM = EDGE && kt + 1 >= KT - 1;       // ... and so is the next one (the section's last, or the next section's first)
           const char* st = sW + slot * QA_STAGE + half * 512 + r31 * 16;
           const int nslot = slot + 1 == R ? 0 : slot + 1;
           const char* stn = sW + nslot * QA_STAGE + half * 512 + r31 * 16;
           if constexpr (sl == 0) {                       // later stages: requested under the previous stage's last MFMAs
             f0 = *reinterpret_cast<const V8*>(st);
-            f1 = *reinterpret_cast<const V8*>(st + 16 * 512);
+            if constexpr (!BM) f1 = *reinterpret_cast<const V8*>(st + 16 * 512);
           }
-          qa_for<0, 8>([&](auto KS_) {
-            constexpr int ks = decltype(KS_)::value;
-            if constexpr (ks == 4) {
-              // middle of stage g: stage g+1 has landed (own pieces; the younger stages may stay in flight) and,
-              // past the barrier, everybody's; every wave is done with stage g-1, whose slot takes stage g+R-1
-              if constexpr (SMALL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-              else if constexpr (!LAST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 3) * 4) : "memory");
-              else if constexpr (ft >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(((ft < R - 2 ? ft : R - 2) - 1) * 4) : "memory");
+          // MFMA 16 of the stage's 32 —
+          // middle of stage g: stage g+1 has landed (own pieces; the younger stages may stay in flight) and,
+          // past the barrier, everybody's; every wave is done with stage g-1, whose slot takes stage g+R-1
+          auto stage_sync = [&]() __attribute__((always_inline)) {
+            if constexpr (SMALL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else if constexpr (!LAST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 3) * 4) : "memory");
+            else if constexpr (ft >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(((ft < R - 2 ? ft : R - 2) - 1) * 4) : "memory");
 #if QA_BARRIER_DRAIN
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (A/B) not needed: the slot refilled behind the barrier is stage g-1's, fully consumed
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (A/B) not needed: the slot refilled behind the barrier is stage g-1's, fully consumed
 #endif
-              __builtin_amdgcn_s_barrier();
-              asm volatile("" ::: "memory");
-            }
-            V8 n0, n1;
-            if constexpr (ks < 7) {
-              n0 = *reinterpret_cast<const V8*>(st + (2 * (ks + 1)) * 512);
-              n1 = *reinterpret_cast<const V8*>(st + (16 + 2 * (ks + 1)) * 512);
-            } else if constexpr (sl + 1 < NSH) {         // stage g+1 landed for everybody at this stage's barrier
-              n0 = *reinterpret_cast<const V8*>(stn);
-              n1 = *reinterpret_cast<const V8*>(stn + 16 * 512);
-            }
-#pragma unroll
-            for (int tt = 0; tt < NT; ++tt) {
-              if constexpr (CLS && sec == 0) {           // q only where the class token lives
-                if (w == 0 && tt == 0) {
-                  acc[tt][0] = Op16<E>::mfma(f0, xf[tt][kt * 8 + ks], acc[tt][0]);
-                  acc[tt][1] = Op16<E>::mfma(f1, xf[tt][kt * 8 + ks], acc[tt][1]);
-                }
-              } else if constexpr (sec < 2) {            // q^T, k^T: rows = features, cols = tokens
-                acc[tt][0] = Op16<E>::mfma(f0, xf[tt][kt * 8 + ks], acc[tt][0]);
-                acc[tt][1] = Op16<E>::mfma(f1, xf[tt][kt * 8 + ks], acc[tt][1]);
-              } else {                                   // v: rows = tokens, cols = features
-                acc[tt][0] = Op16<E>::mfma(xf[tt][kt * 8 + ks], f0, acc[tt][0]);
-                acc[tt][1] = Op16<E>::mfma(xf[tt][kt * 8 + ks], f1, acc[tt][1]);
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+          };
+          // behind the stage barrier: the slot of stage g-1 is free — one piece behind MFMA 20, 24, 28 and 32
+          auto stage_piece = [&](auto P_) __attribute__((always_inline)) {
+            if constexpr (SMALL) { if (g + R - 1 < gtotal) issue_piece_asm(P_); }
+            else if constexpr (!LAST || ft >= R - 1) issue_piece_asm(P_);
+          };
+          auto mfma_into = [&](auto TT_, auto I_, V8 f, V8 x) __attribute__((always_inline)) {
+            constexpr int tt = decltype(TT_)::value, i = decltype(I_)::value;
+            if constexpr (sec < 2) return Op16<E>::mfma(f, x, acc[tt][i]);        // q^T, k^T: rows = features, cols = tokens
+            else return Op16<E>::mfma(x, f, acc[tt][i]);                         // v: rows = tokens, cols = features
+          };
+          if constexpr (!BM) {
+            qa_for<0, 8>([&](auto KS_) {
+              constexpr int ks = decltype(KS_)::value;
+              if constexpr (ks == 4) stage_sync();
+              V8 n0, n1;
+              if constexpr (ks < 7) {
+                n0 = *reinterpret_cast<const V8*>(st + (2 * (ks + 1)) * 512);
+                n1 = *reinterpret_cast<const V8*>(st + (16 + 2 * (ks + 1)) * 512);
+              } else if constexpr (sl + 1 < NSH) {       // stage g+1 landed for everybody at this stage's barrier
+                n0 = *reinterpret_cast<const V8*>(stn);
+                if constexpr (!NEXT_BM) n1 = *reinterpret_cast<const V8*>(stn + 16 * 512);
               }
-            }
-            if constexpr (ks >= 4) {                     // behind the stage barrier: the slot of stage g-1 is free
-              if constexpr (SMALL) { if (g + R - 1 < gtotal) issue_piece_asm(std::integral_constant<int, ks - 4>{}); }
-              else if constexpr (!LAST || ft >= R - 1) issue_piece_asm(std::integral_constant<int, ks - 4>{});
-            }
-            if constexpr (ks < 7 || sl + 1 < NSH) { f0 = n0; f1 = n1; }
-          });
+              qa_for<0, NT>([&](auto TT_) {
+                constexpr int tt = decltype(TT_)::value;
+                if constexpr (CLS && sec == 0) {         // q only where the class token lives
+                  if (w == 0 && tt == 0) {
+                    acc[tt][0] = mfma_into(TT_, std::integral_constant<int, 0>{}, f0, xf[tt][kt * 8 + ks]);
+                    acc[tt][1] = mfma_into(TT_, std::integral_constant<int, 1>{}, f1, xf[tt][kt * 8 + ks]);
+                  }
+                } else {
+                  acc[tt][0] = mfma_into(TT_, std::integral_constant<int, 0>{}, f0, xf[tt][kt * 8 + ks]);
+                  acc[tt][1] = mfma_into(TT_, std::integral_constant<int, 1>{}, f1, xf[tt][kt * 8 + ks]);
+                }
+              });
+              if constexpr (ks >= 4) stage_piece(std::integral_constant<int, ks - 4>{});
+              if constexpr (ks < 7 || sl + 1 < NSH) f0 = n0;
+              if constexpr (ks < 7 || (sl + 1 < NSH && !NEXT_BM)) f1 = n1;
+            });
+          } else {
+            // Row-block-major: ONE rolling fragment (f0), read in the order row block 0's k-steps, row block 1's k-steps, the next stage's
+            // first; the counted wait + barrier at the block switch (MFMA 16 of 32 as before).  The gaps of a block's MFMAs host the other
+            // block's hand-over, a part per gap, pinned with sched_barriers (as p_part in the attention):
+            //   first stage of k / v   block 0 hosts the PREVIOUS section's row block 1, which block 1's MFMAs overwrite only afterwards;
+            //   last stage             block 1 hosts this section's row block 0, final since the block switch.  K / V stores of a head
+            //                          thereby move in front of the section's end, never in front of the head's first stage barrier, which
+            //                          every wave passes only after its attention reads of the previous head's K / V.
+            constexpr bool HOST_PREV = kt == 0 && sec > 0, HOST_OWN = kt == KT - 1;
+            qa_for<0, 2>([&](auto BLK_) {
+              constexpr int blk = decltype(BLK_)::value;
+              constexpr bool HOSTING = blk == 0 ? HOST_PREV : HOST_OWN;
+              qa_for<0, 8>([&](auto KS_) {
+                constexpr int ks = decltype(KS_)::value;
+                if constexpr (blk == 1 && ks == 0) stage_sync();
+                V8 n0, n1;
+                if constexpr (ks < 7) n0 = *reinterpret_cast<const V8*>(st + (16 * blk + 2 * (ks + 1)) * 512);
+                else if constexpr (blk == 0) n0 = *reinterpret_cast<const V8*>(st + 16 * 512);
+                else if constexpr (sl + 1 < NSH) {       // stage g+1 landed for everybody at this stage's barrier
+                  n0 = *reinterpret_cast<const V8*>(stn);
+                  if constexpr (!NEXT_BM) n1 = *reinterpret_cast<const V8*>(stn + 16 * 512);
+                }
+                qa_for<0, NT>([&](auto TT_) {
+                  constexpr int tt = decltype(TT_)::value;
+                  if constexpr (kt == 0 && ks == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[tt][blk][r] = 0.f;
+                  }
+                  if constexpr (CLS && sec == 0) {       // q only where the class token lives
+                    if (w == 0 && tt == 0) acc[tt][blk] = mfma_into(TT_, BLK_, f0, xf[tt][kt * 8 + ks]);
+                  } else {
+                    acc[tt][blk] = mfma_into(TT_, BLK_, f0, xf[tt][kt * 8 + ks]);
+                  }
+                  if constexpr (HOSTING) {
+                    constexpr int gi = ks * NT + tt, fr = gi >> 2;   // gap, fragment (tile, m) of the hosted row block: 8 NT gaps = 2 NT fragments x 4 parts
+                    __builtin_amdgcn_sched_barrier(0);
+                    hand_part(std::integral_constant<int, (blk == 0 ? sec - 1 : sec)>{}, std::integral_constant<int, 1 - blk>{},
+                              std::integral_constant<int, (fr >> 1)>{}, std::integral_constant<int, (fr & 1)>{}, std::integral_constant<int, (gi & 3)>{});
+                    __builtin_amdgcn_sched_barrier(0);
+                  }
+                });
+                // the bias of the next hosted row block, two k-steps ahead of its first part
+                if constexpr (HOST_OWN && ks == 6) {
+                  if constexpr (blk == 0) hand_bias(SEC_, std::integral_constant<int, 0>{});
+                  else if constexpr (sec < 2) hand_bias(SEC_, std::integral_constant<int, 1>{});
+                }
+                if constexpr (blk == 1 && (ks & 1) == 0) stage_piece(std::integral_constant<int, ks / 2>{});
+                if constexpr (ks < 7 || blk == 0 || sl + 1 < NSH) f0 = n0;
+                if constexpr (blk == 1 && ks == 7 && sl + 1 < NSH && !NEXT_BM) f1 = n1;
+              });
+            });
+          }
           if constexpr (SMALL) { if (g + R - 1 < gtotal) issue_advance(); }
           else if constexpr (!LAST || ft >= R - 1) issue_advance();
           slot = slot + 1 == R ? 0 : slot + 1;
           ++g;
         });
-        // ---- accumulators (+ bias) -> 16-bit operand fragments.  Registers 8m..8m+7 of tile i = fragment (i, m).
-#pragma unroll
-        for (int tt = 0; tt < NT; ++tt) {
-          const int tile = 2 * w + tt;
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-              u32x4 p;
-              if constexpr (sec < 2) {
-                const float* bp = sBias + sec * D + h * 64 + i * 32 + 4 * half;
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp + 8 * (2 * m));
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(bp + 8 * (2 * m + 1));
-                const u32x2 lo = pack4<E>(acc[tt][i][8 * m] + b0[0], acc[tt][i][8 * m + 1] + b0[1], acc[tt][i][8 * m + 2] + b0[2], acc[tt][i][8 * m + 3] + b0[3]);
-                const u32x2 hi = pack4<E>(acc[tt][i][8 * m + 4] + b1[0], acc[tt][i][8 * m + 5] + b1[1], acc[tt][i][8 * m + 6] + b1[2], acc[tt][i][8 * m + 7] + b1[3]);
-                p = u32x4{lo[0], lo[1], hi[0], hi[1]};
-              } else {
-                const float bv = sBias[2 * D + h * 64 + i * 32 + r31];
-                const u32x2 lo = pack4<E>(acc[tt][i][8 * m] + bv, acc[tt][i][8 * m + 1] + bv, acc[tt][i][8 * m + 2] + bv, acc[tt][i][8 * m + 3] + bv);
-                const u32x2 hi = pack4<E>(acc[tt][i][8 * m + 4] + bv, acc[tt][i][8 * m + 5] + bv, acc[tt][i][8 * m + 6] + bv, acc[tt][i][8 * m + 7] + bv);
-                p = u32x4{lo[0], lo[1], hi[0], hi[1]};
-              }
-              if constexpr (sec == 0) qf[tt][2 * i + m] = __builtin_bit_cast(V8, p);
-              else if (tile < NTT) {
-                if constexpr (sec == 1) *reinterpret_cast<u32x4*>(sK + ((tile * 4 + 2 * i + m) * 64 + lane) * 16) = p;
-                else *reinterpret_cast<u32x4*>(sV + (((tile * 2 + m) * 2 + i) * 64 + lane) * 16) = p;
-              }
-            }
-          }
+        if constexpr (!EDGE) {
+          hand_block(SEC_, std::integral_constant<int, 0>{});
+          hand_block(SEC_, std::integral_constant<int, 1>{});
+        } else if constexpr (sec == 2) {
+          hand_block(SEC_, std::integral_constant<int, 1>{});
         }
         QA_STAMP_AT(1 + sec)
       });

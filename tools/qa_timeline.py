@@ -2,7 +2,9 @@
 """Per-head timeline of the fused qkv + attention kernel from a -DQA_STAMP build (tools/ab_build.sh qastamp "-DQA_STAMP" qkvattn.hip):
    EFFOCR_HIP_LIB=$PWD/tools/ab/lib_qastamp.so python tools/qa_timeline.py [batch]
 Every wave stamps s_memtime at the milestones of a head (the last head it ran stays in the table); prints the mean length of each segment
-per wave index (waves 0-2 own two full token tiles, wave 3 owns tile 6 + the dummy) and the whole head."""
+per wave index (waves 0-2 own two full token tiles, wave 3 owns tile 6 + the dummy) and the whole head.
+With QA_EDGE_BLOCK_MAJOR (the default) the q / k / v stamps sit behind each section's last ring stage: the second half of q's and k's
+hand-over runs inside the next section's first stage and is counted there; only v's figure still ends with an exposed hand-over."""
 import ctypes, os, sys
 import numpy as np
 import torch
