@@ -59,12 +59,12 @@ class HipClassifierHead:
         return self._run(emb, False, True)[1]
 
 
-def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECISION, img_size=224):
+def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECISION, img_size=224, call_size_invariant=False):
     """Drop-in for models/classifiers.py:74 ``AutoClassifierFactory(backend, modelpath, n_classes)``: returns a class whose instances
     behave like the reference's ``AutoClassifier`` at its call sites — ``.load(ckpt)`` (``net.`` keys; infer_effocr.py:177),
     ``.to(device)`` / ``.eval()``, ``model(x[B,3,H,W]) -> logits [B, n_classes]`` float32 on the input's device (:330-332) — plus
-    ``predict(x) -> ids [B]`` through the fused argmax.  ``precision`` / ``img_size`` are extensions with the encoders' defaults;
-    the head itself always runs in fp32."""
+    ``predict(x) -> ids [B]`` through the fused argmax.  ``precision`` / ``img_size`` / ``call_size_invariant`` are extensions with the
+    encoders' defaults; the head itself always runs in fp32, bitwise independent of the call size."""
     if backend != "timm":
         raise NotImplementedError
     W.embed_dim(modelpath)          # raises NotImplementedError for unknown architectures
@@ -134,7 +134,8 @@ def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECI
         @property
         def engine(self):
             if self._engine is None:
-                self._engine = make_encoder(self.model_name, self._sd, img_size=img_size, precision=precision, device=self._device)
+                self._engine = make_encoder(self.model_name, self._sd, img_size=img_size, precision=precision, device=self._device,
+                                            call_size_invariant=call_size_invariant)
             return self._engine
 
         @property
@@ -154,6 +155,11 @@ def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECI
         def predict(self, x):
             """int64 ids [B] = forward(x).argmax(-1), through the fused argmax (no logits are written)."""
             return self.head.predict(self.embed(x))
+
+        @property
+        def call_size_invariant(self):
+            """The engine's property of that name (HipEncoder.call_size_invariant); builds the engine."""
+            return self.engine.call_size_invariant
 
         def check_status(self):
             """Raise if any forward since the last check produced a non-finite embedding (HipEncoder.check_status)."""

@@ -78,6 +78,7 @@ struct effocr_encoder {
   int panel_rows = 128;             // row-panel height: 128 (1 workgroup/CU) or 64 (2 workgroups/CU)
   int use_panel = 1;                // 0: force the K-streaming GEMM + standalone LayerNorm path (A/B switch)
   int chunk = 0;                    // crops per internal sub-batch of the ViT forward (0 = whole batch; ConvNeXt: 0 = cnx_chunk's default)
+  int call_size_invariant = 0;      // 1: every selection that changes a row's arithmetic is a function of the layer alone (DESIGN.md "Call-size-invariant mode"): the fused MLP runs whole 128-token panels for every M, the convolutions never split K.  Overrides tail_split / split6 / pair_parts / mlp_pair where they reach the fused MLP without overwriting them
   int prof_mode = 0;                // 0 off, 1 every class, 2 only prof_only
   std::string prof_only;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
@@ -652,7 +653,7 @@ int vit_forward(effocr_encoder* e, const void* x, int x16, int B, float* emb, in
   const bool projf = mlpf && e->use_projf;
   // one image per workgroup at a time: worth it from ~3/4 of a round of CUs on; small batches (the reference's 64-crop calls)
   // keep the token-panel kernels, which spread 64 x 197 tokens over every CU.  use_qkvattn = 2 forces it (tests).
-  const bool qaf = blk && panel && mlpf && qkv_attn_supported(prec, D, T) && (e->use_qkvattn == 2 || (e->use_qkvattn == 1 && B >= e->qa_min_batch));
+  const bool qaf = blk && panel && mlpf && qkv_attn_supported(prec, D, T) && (e->use_qkvattn == 2 || (e->use_qkvattn == 1 && (e->call_size_invariant || B >= e->qa_min_batch)));   // (call-size-invariant mode: the choice between the two attention paths may not follow B)
   const bool g3 = blk && e->use_gemm3 && gemm3_supported(prec, D, e->vit.mlp);
   const bool patchf = blk && e->use_patchf && patch_embed_fused_supported(prec, D);
   if (!patchf && (rc = timed(e, "im2col_patch16", 0.0, s, [&] { return im2col_patch16(prec, x, x16, B, e->img, e->img, hb, s); }))) return rc;
@@ -710,6 +711,7 @@ int vit_forward(effocr_encoder* e, const void* x, int x16, int B, float* emb, in
         m.x = xs; m.gamma = F(L.ln2w); m.beta = F(L.ln2b); m.eps = 1e-6f; m.W1b = wb + L.fc1w_b; m.b1 = F(L.fc1b);
         m.W2p = wb + L.fc2w_pp; m.b2 = F(L.fc2b_p); m.b2_logical = F(L.fc2b); m.M = M; m.D = D; m.H = e->vit.mlp; m.rows_alloc = (int)w.rows;
         m.partial = reinterpret_cast<float*>(hb); m.partial_bytes = w.hbytes; m.no_tail_split = !e->tail_split; m.no_split6 = !e->split6; m.pair = e->mlp_pair; m.no_pair_parts = !e->pair_parts; m.stagger = e->mlp_stagger; m.stagger_min_rounds = e->mlp_stagger_min_rounds;   // the hidden buffer is free on this path
+        if (e->call_size_invariant) { m.no_tail_split = 1; m.pair = -1; }   // whole panels only: no hidden split (a reordered fc2 sum), no pair form
         if (projf) {                                     // attn.proj + residual runs inside the same kernel, in front
           m.A = att; m.Wpp = wb + L.projw_pp; m.bp = F(L.projb_p);
           if (i + 1 == e->vit.depth && e->cls_only_last) {
@@ -993,7 +995,8 @@ int resnet_forward(effocr_encoder* e, const float* x, int B, float* emb, int l2,
   a.in = col; a.w = WT(e->convs[0]); a.bias = BS(e->convs[0]); a.resid = nullptr; a.out = bufs[0];
   a.B = B * OH * OH; a.H = 1; a.W = 1; a.Cin = CONV1_KPAD; a.Cout = 64; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
   a.OH = 1; a.OW = 1; a.relu = 1;
-  float* split = reinterpret_cast<float*>(ws + w.split);
+  // call-size-invariant mode: no partial buffer, so conv2d_nhwc never splits K (its split count follows the launch's tile count)
+  float* split = e->call_size_invariant ? nullptr : reinterpret_cast<float*>(ws + w.split);
   a.partial = split; a.partial_bytes = CONV_SPLIT_BYTES;
   if ((rc = conv2d_nhwc(a, s))) return rc;
   H = OH; OH = (H + 2 - 3) / 2 + 1;
@@ -1162,6 +1165,10 @@ int effocr_encoder_set_option(effocr_encoder_t* enc, const char* name, int value
   if (n == "mlp_stagger_min_rounds") { enc->mlp_stagger_min_rounds = value < 1 ? 1 : value; return EFFOCR_OK; }
   if (n == "mlp_stagger") { enc->mlp_stagger = value < 0 ? 0 : value; return EFFOCR_OK; }
   if (n == "panel_rows") { if (value != 64 && value != 128) return fail(EFFOCR_EINVAL, "set_option: panel_rows must be 64 or 128"); enc->panel_rows = value; return EFFOCR_OK; }
+  if (n == "call_size_invariant") {
+    if (value != 0 && value != 1) return fail(EFFOCR_EINVAL, "set_option: call_size_invariant must be 0 or 1");
+    enc->call_size_invariant = value; return EFFOCR_OK;
+  }
   if (n == "chunk") { if (value < 0) return fail(EFFOCR_EINVAL, "set_option: chunk < 0"); enc->chunk = value; return EFFOCR_OK; }
   return fail(EFFOCR_EINVAL, "set_option: unknown option '" + n + "'");
 }

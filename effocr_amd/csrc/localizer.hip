@@ -63,6 +63,7 @@ struct effocr_localizer {
   const char* wdev = nullptr;
   int64_t npred = 0;
   int direct_stem = 1;                                   // 0: the stem through im2col + the 1x1 implicit GEMM (A/B)
+  int call_size_invariant = 0;                           // 1: no convolution splits K (the split count follows the call's tile count): a row of predictions is a function of its image alone
   int bf16 = 0;                                          // 1: bf16-operand MFMAs for every convolution with an activation (Detect's 1x1 heads stay fp32)
 };
 
@@ -343,6 +344,10 @@ int effocr_localizer_set_option(effocr_localizer_t* loc, const char* name, int v
   if (!loc || !name) return fail(EFFOCR_EINVAL, "localizer_set_option: NULL argument");
   if (std::string(name) == "bf16_operands") { loc->bf16 = value != 0; return EFFOCR_OK; }
   if (std::string(name) == "direct_stem") { loc->direct_stem = value != 0; return EFFOCR_OK; }
+  if (std::string(name) == "call_size_invariant") {
+    if (value != 0 && value != 1) return fail(EFFOCR_EINVAL, "localizer_set_option: call_size_invariant must be 0 or 1");
+    loc->call_size_invariant = value; return EFFOCR_OK;
+  }
   return fail(EFFOCR_EINVAL, std::string("localizer_set_option: unknown option '") + name + "'");
 }
 int64_t effocr_localizer_num_predictions(const effocr_localizer_t* loc) { return loc ? loc->npred : 0; }
@@ -390,7 +395,7 @@ int effocr_localizer_forward(effocr_localizer_t* loc, const float* x_dev, int ba
         a.out = P(op.out.buf); a.B = batch * o.H * o.W; a.H = 1; a.W = 1; a.Cin = c.kpad; a.Cout = c.cout_pad; a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
         a.OH = 1; a.OW = 1; a.silu = c.act; a.out_ld = o.C; a.out_off = op.out.off;
         if (loc->bf16 && c.act) a.w16 = loc->wdev + c.w16_off;
-        a.partial = reinterpret_cast<float*>(ws + w.split); a.partial_bytes = LOC_SPLIT_BYTES;
+        a.partial = loc->call_size_invariant ? nullptr : reinterpret_cast<float*>(ws + w.split); a.partial_bytes = LOC_SPLIT_BYTES;
         if ((rc = conv2d_nhwc(a, s))) return rc;
         break;
       }
@@ -405,7 +410,7 @@ int effocr_localizer_forward(effocr_localizer_t* loc, const float* x_dev, int ba
         a.B = batch; a.H = i.H; a.W = i.W; a.Cin = c.cin_st; a.Cout = c.cout_pad; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
         a.OH = o.H; a.OW = o.W; a.silu = c.act;
         if (loc->bf16 && c.act) a.w16 = loc->wdev + c.w16_off;
-        a.partial = reinterpret_cast<float*>(ws + w.split); a.partial_bytes = LOC_SPLIT_BYTES;
+        a.partial = loc->call_size_invariant ? nullptr : reinterpret_cast<float*>(ws + w.split); a.partial_bytes = LOC_SPLIT_BYTES;
         if ((rc = conv2d_nhwc(a, s))) return rc;
         break;
       }

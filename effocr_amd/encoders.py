@@ -34,10 +34,18 @@ class HipEncoder:
     """Device-resident encoder: C-ABI handle + weight blob + one grow-only workspace PER HIP STREAM (the Python lock
     covers only the enqueue; two threads forwarding on different streams must not share activation buffers)."""
 
-    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
+    # architectures of libeffocr_hip.so whose kernels never chose by the call size: the property holds without the option
+    _ALWAYS_INVARIANT = ("convnext_tiny", "mobilenetv3_small_050")
+
+    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None, call_size_invariant=False):
         self._create(_lib.lib, "effocr_encoder", lambda rc, what: _lib.check(rc, what, self._L), arch, state_dict, img_size, precision, device)
         # calls of 192..640 crops run as 2-4 concurrent sub-batches of ~128 crops on side streams (ViT-S, 16-bit modes; forward_split below)
         self.split_streams = True
+        # call_size_invariant=True: a crop's embedding is bitwise the same in every call size, position and sub-batching (the library's
+        # "call_size_invariant" option, DESIGN.md "Call-size-invariant mode"; set_option("call_size_invariant", 0 | 1) switches it later)
+        self._call_size_invariant = False
+        if call_size_invariant and arch not in self._ALWAYS_INVARIANT:
+            self.set_option("call_size_invariant", 1)
 
     def _create(self, load, prefix, check, arch, state_dict, img_size, precision, device):
         """Create the handle, set every parameter and upload the packed weights through the entry points ``<prefix>_*`` of the library
@@ -88,6 +96,14 @@ class HipEncoder:
 
     def set_option(self, name, value):
         _lib.check(self._L.effocr_encoder_set_option(self._h, name.encode(), int(value)), "effocr_encoder_set_option", self._L)
+        if name == "call_size_invariant":
+            self._call_size_invariant = bool(value)
+
+    @property
+    def call_size_invariant(self):
+        """True when a crop's embedding is bitwise independent of the call it travels in: the mode is on, or the architecture has the
+        property in every mode (convnext_tiny, mobilenetv3_small_050)."""
+        return self._call_size_invariant or self.arch in self._ALWAYS_INVARIANT
 
     def workspace_bytes(self, batch):
         return int(self._L.effocr_encoder_workspace_bytes(self._h, int(batch)))
@@ -284,7 +300,8 @@ class _FamilyEncoder(HipEncoder):
     _family = None                           # "swin": the entry points effocr_swin_*
     _label = None                            # the name the messages use
 
-    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
+    def __init__(self, arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None, call_size_invariant=False):
+        # (call_size_invariant: accepted and ignored — these libraries' kernels never choose by the call size)
         self._create(getattr(_lib, f"{self._family}_lib"), f"effocr_{self._family}", getattr(_lib, f"{self._family}_check"),
                      arch, state_dict, img_size, precision, device)
 
@@ -312,6 +329,10 @@ class _FamilyEncoder(HipEncoder):
 
     def workspace_bytes(self, batch):
         return int(self._fn("workspace_bytes")(self._h, int(batch)))
+
+    @property
+    def call_size_invariant(self):
+        return True
 
     @property
     def crop_dtype(self):
@@ -374,17 +395,18 @@ class EfficientNetEncoder(_FamilyEncoder):
         self._status_call("reset_status")
 
 
-def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None):
+def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None, call_size_invariant=False):
     """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, ResNetEncoder (libeffocr_resnet.so) for resnet34 / resnet50,
     MobileNetV3Encoder (libeffocr_mnv3.so) for mobilenetv3_small_075 / _small_100 / _large_100, EfficientNetEncoder
     (libeffocr_effnet.so) for efficientnet_b0 / tf_efficientnet_b0, HipEncoder (libeffocr_hip.so) for every other architecture
-    (mobilenetv3_small_050 among them)."""
+    (mobilenetv3_small_050 among them).  ``call_size_invariant``: HipEncoder's mode of that name; the other engines have the property
+    in every mode and ignore the keyword."""
     cls = (SwinEncoder if W.is_swin(arch) else ResNetEncoder if W.is_resnet_lib(arch) else MobileNetV3Encoder if W.is_mnv3_lib(arch)
            else EfficientNetEncoder if W.is_efficientnet(arch) else HipEncoder)
-    return cls(arch, state_dict, img_size=img_size, precision=precision, device=device)
+    return cls(arch, state_dict, img_size=img_size, precision=precision, device=device, call_size_invariant=call_size_invariant)
 
 
-def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size=224):
+def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size=224, call_size_invariant=False):
     """Drop-in for models/encoders.py:50 ``AutoEncoderFactory(backend, modelpath)``.
 
     Only the ``"timm"`` backend is implemented, with the architectures BASELINE.json names (resnet18, vit_small_patch16_224,
@@ -393,7 +415,7 @@ def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size
     ``mobilenetv3_large_100``, ``efficientnet_b0`` and ``tf_efficientnet_b0`` (the "hf" branch and XcitDinoEncoder are out
     of scope); anything else raises NotImplementedError exactly like the reference's ``else`` branch
     (encoders.py:93-95).
-    ``precision`` / ``img_size`` are extensions with reference-compatible defaults.
+    ``precision`` / ``img_size`` / ``call_size_invariant`` (HipEncoder) are extensions with reference-compatible defaults.
     """
     if backend != "timm":
         raise NotImplementedError
@@ -462,11 +484,16 @@ def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size
         def engine(self):
             if self._engine is None:
                 self._engine = make_encoder(self.model_name, self._sd, img_size=img_size, precision=precision,
-                                            device=self._device)
+                                            device=self._device, call_size_invariant=call_size_invariant)
             return self._engine
 
         def forward(self, x):
             return self.engine.forward(x, normalize=False)
+
+        @property
+        def call_size_invariant(self):
+            """The engine's property of that name (HipEncoder.call_size_invariant); builds the engine."""
+            return self.engine.call_size_invariant
 
         def check_status(self):
             """Raise if any forward since the last check produced a non-finite embedding (HipEncoder.check_status)."""

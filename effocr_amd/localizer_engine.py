@@ -196,7 +196,7 @@ def _load_state_dict(model_path):
 class HipLocalizer:
     """Device-resident YOLOv5 (any v6 scale n / s / m / l / x): C-ABI handle + weight blob + per-stream workspaces."""
 
-    def __init__(self, state_dict, input_shape=(640, 640), device=None, precision="fp32", arch=None):
+    def __init__(self, state_dict, input_shape=(640, 640), device=None, precision="fp32", arch=None, call_size_invariant=False):
         # arch (optional): "yolov5n" ... "yolov5x"; must agree with the scale the state dict has (yolov5_scale)
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
@@ -225,12 +225,23 @@ class HipLocalizer:
             self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             _lib.check(self._L.effocr_localizer_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_localizer_upload", self._L)
         self.set_option("bf16_operands", 1 if precision == "bf16" else 0)
+        # call_size_invariant=True: an image's predictions are bitwise the same in every batch size and position (no convolution
+        # splits K; DESIGN.md "Call-size-invariant mode")
+        self._call_size_invariant = False
+        if call_size_invariant:
+            self.set_option("call_size_invariant", 1)
         self.num_predictions = int(self._L.effocr_localizer_num_predictions(self._h))
         self._ws = {}
         self._lock = threading.Lock()
 
     def set_option(self, name, value):
         _lib.check(self._L.effocr_localizer_set_option(self._h, name.encode(), int(value)), "effocr_localizer_set_option", self._L)
+        if name == "call_size_invariant":
+            self._call_size_invariant = bool(value)
+
+    @property
+    def call_size_invariant(self):
+        return self._call_size_invariant
 
     def __del__(self):
         try:
@@ -339,7 +350,7 @@ class HipLocalizer:
 class EffLocalizer:
 
     def __init__(self, model_path, iou_thresh=0.01, conf_thresh=0.30, vertical=False, num_cores=None, providers=None,
-                 input_shape=(640, 640), model_backend='yolo', device=None, precision="fp32", arch=None):
+                 input_shape=(640, 640), model_backend='yolo', device=None, precision="fp32", arch=None, call_size_invariant=False):
         # precision (extension): "fp32" = fp32 MFMA operands (the oracle's arithmetic), "bf16" = bf16-rounded operands for every
         # convolution with an activation, fp32 accumulation and fp32 Detect heads (2-3x the network throughput)
         # arch (extension): "yolov5n" ... "yolov5x" or None; the scale is read from the state dict and must agree (HipLocalizer)
@@ -351,10 +362,14 @@ class EffLocalizer:
         self._input_shape = (int(input_shape[0]), int(input_shape[1]))
         self._model_backend = model_backend
         self._eng_net = HipLocalizer(_load_state_dict(model_path), input_shape=self._input_shape, device=device, precision=precision,
-                                     arch=arch)
+                                     arch=arch, call_size_invariant=call_size_invariant)
 
     def __call__(self, imgs):
         return self.run(imgs)
+
+    @property
+    def call_size_invariant(self):
+        return self._eng_net.call_size_invariant
 
     def load_localizer_img(self, input_path):
         """localizer_engine.py:75-85 with PIL instead of cv2.imread (cv2 is not installed): RGB in, so no channel swap."""

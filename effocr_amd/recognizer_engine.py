@@ -42,7 +42,7 @@ class _Lane:
 class EffRecognizer:
 
     def __init__(self, model, num_cores=None, providers=None, arch=None, precision=DEFAULT_PRECISION, img_size=224,
-                 device=None, lanes=4, copiers=4, slices=8, staging="direct"):
+                 device=None, lanes=4, copiers=4, slices=8, staging="direct", call_size_invariant=False):
         # num_cores / providers are ORT knobs (recognizer_engine.py:10-15): accepted and ignored.
         self.num_cores, self.providers = num_cores, providers
         if isinstance(model, dict):
@@ -50,7 +50,9 @@ class EffRecognizer:
         else:
             sd = W.load_checkpoint(model)
         self.arch = arch or W.infer_arch(sd)
-        self._eng_net = make_encoder(self.arch, sd, img_size=img_size, precision=precision, device=device)
+        # call_size_invariant (extension): embs[i] bitwise independent of how the caller batches (HipEncoder)
+        self._eng_net = make_encoder(self.arch, sd, img_size=img_size, precision=precision, device=device,
+                                     call_size_invariant=call_size_invariant)
         # One instance is shared by N Python threads in the reference (infer_effocr_onnx_multi.py:207-223,350-364).
         # `lanes` calls can be in flight at once; further callers wait for a free lane.  ctypes releases the GIL during
         # the enqueue and torch releases it during copies / synchronisation, so the threads really overlap:
@@ -77,6 +79,10 @@ class EffRecognizer:
     @property
     def img_size(self):
         return self._eng_net.img_size
+
+    @property
+    def call_size_invariant(self):
+        return self._eng_net.call_size_invariant
 
     @property
     def crop_dtype(self):

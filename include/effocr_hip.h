@@ -154,7 +154,13 @@ int effocr_encoder_set_chunk(effocr_encoder_t* enc, int crops_per_chunk);
  *                 attn.proj / mlp.fc2 also write the new residual row as 16-bit operands + per-row partial sums, attn.qkv / mlp.fc1
  *                 multiply by W . diag(gamma) and finish rstd (acc - mean s) + (b + W beta) in their epilogues: 1 LayerNorm launch
  *                 per forward instead of 24 (0: LayerNorm launches, A/B switch)
- *   "panel_rows"  [128] row-panel height, 64 or 128;  "chunk" (= set_chunk);  "debug" (experiment hooks) */
+ *   "panel_rows"  [128] row-panel height, 64 or 128;  "chunk" (= set_chunk);  "debug" (experiment hooks)
+ *   "call_size_invariant" [0] 1 = the output row of a crop is a function of its pixels, the weights, the precision and the image size
+ *                 only: the same bits in every call size, at every position, under "chunk" (ViT-S, 16-bit modes: the fused MLP runs whole
+ *                 128-token panels for every row count; resnet18: no convolution splits K).  It overrides "tail_split", "split6",
+ *                 "pair_parts" and "mlp_pair" where they reach the fused MLP, and "qa_min_batch" (taken as 1: the choice between the two
+ *                 attention paths may not follow the batch), without overwriting them: 0 restores what the caller had
+ *                 set.  Any value but 0 / 1: EFFOCR_EINVAL.  Cost: DESIGN.md "Call-size-invariant mode" */
 int effocr_encoder_set_option(effocr_encoder_t* enc, const char* name, int value);
 
 /* HIP-event profiler for bench.py's roofline object: while armed, every launch of the selected
@@ -291,7 +297,9 @@ int effocr_localizer_upload(effocr_localizer_t* loc, void* weights_dev, size_t b
  * upload, activations in the stage loader) on v_mfma_f32_32x32x16_bf16, fp32 accumulation / bias / SiLU / residual; Detect's 1x1
  * heads keep fp32 operands.  0 = fp32 operands everywhere (v_mfma_f32_32x32x2_f32: the oracle's arithmetic up to summation order).
  * "direct_stem" [1]: the stem Conv(3, c, 6, 2, 2) as a direct kernel from the NCHW input; 0 = im2col rows + the implicit GEMM (A/B
- * switch; set it before effocr_localizer_workspace_bytes — the im2col rows, 840 MB at 16 images, exist only on that path). */
+ * switch; set it before effocr_localizer_workspace_bytes — the im2col rows, 840 MB at 16 images, exist only on that path).
+ * "call_size_invariant" [0]: 1 = no convolution splits K (the split count follows the call's tile count), so an image's predictions are
+ * the same bits in every batch size and at every position of the batch; any value but 0 / 1: EFFOCR_EINVAL. */
 int effocr_localizer_set_option(effocr_localizer_t* loc, const char* name, int value);
 int64_t effocr_localizer_num_predictions(const effocr_localizer_t* loc);
 int effocr_localizer_num_outputs(const effocr_localizer_t* loc);             /* 5 + num_classes */
