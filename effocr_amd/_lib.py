@@ -312,11 +312,34 @@ def effnet_lib():
     return _load_family(EFFNET_SO_PATH, "effnet", EFFNET_ABI_VERSION, _effnet_signatures(), "EfficientNet encoder")
 
 
+# libeffocr_beit.so (include/effocr_beit.h): the BEiT base encoders beit_base_patch16_224 / beitv2_base_patch16_224 (attention with a
+# relative-position bias; it carries its own copies of the GEMMs and of the ViT helper kernels, hidden).
+BEIT_SO_PATH = os.path.join(_HERE, "libeffocr_beit.so")
+BEIT_ABI_VERSION = 1     # == EFFOCR_BEIT_ABI_VERSION of include/effocr_beit.h
+
+
+def _beit_signatures():
+    c = ctypes
+    vp, i32 = c.c_void_p, c.c_int
+    sig = _encoder_signatures("beit")
+    sig["effocr_beit_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_beit_op_attn"] = (i32, [vp, vp, i32, i32, i32, i32, vp, vp])                    # test entry point
+    return sig
+
+
+BEIT_EXPORTS = tuple(sorted(_beit_signatures()))
+
+
+def beit_lib():
+    return _load_family(BEIT_SO_PATH, "beit", BEIT_ABI_VERSION, _beit_signatures(), "BEiT encoder")
+
+
 head_check = _family_check("head")
 swin_check = _family_check("swin")
 resnet_check = _family_check("resnet")
 mnv3_check = _family_check("mnv3")
 effnet_check = _family_check("effnet")
+beit_check = _family_check("beit")
 
 
 def check(rc, what="", handle=None):

@@ -395,14 +395,26 @@ class EfficientNetEncoder(_FamilyEncoder):
         self._status_call("reset_status")
 
 
+class BeitEncoder(_FamilyEncoder):
+    """libeffocr_beit.so: beit_base_patch16_224 / beitv2_base_patch16_224 (and the miniature beit_tiny_test) at any img_size that is a
+    multiple of 16 from 16 to 224 (the patch im2col reads the fp32 crops and rounds to the operand type).  The two names share keys,
+    shapes and code.  Default sub-batch: a workspace under 1 GB, at most 256 crops."""
+    _family, _label = "beit", "BEiT"
+
+    def reset_status(self):
+        """Clear the current stream's status word without reading it (asynchronous)."""
+        self._status_call("reset_status")
+
+
 def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None, call_size_invariant=False):
     """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, ResNetEncoder (libeffocr_resnet.so) for resnet34 / resnet50,
     MobileNetV3Encoder (libeffocr_mnv3.so) for mobilenetv3_small_075 / _small_100 / _large_100, EfficientNetEncoder
-    (libeffocr_effnet.so) for efficientnet_b0 / tf_efficientnet_b0, HipEncoder (libeffocr_hip.so) for every other architecture
+    (libeffocr_effnet.so) for efficientnet_b0 / tf_efficientnet_b0, BeitEncoder (libeffocr_beit.so) for beit_base_patch16_224 /
+    beitv2_base_patch16_224, HipEncoder (libeffocr_hip.so) for every other architecture
     (mobilenetv3_small_050 among them).  ``call_size_invariant``: HipEncoder's mode of that name; the other engines have the property
     in every mode and ignore the keyword."""
     cls = (SwinEncoder if W.is_swin(arch) else ResNetEncoder if W.is_resnet_lib(arch) else MobileNetV3Encoder if W.is_mnv3_lib(arch)
-           else EfficientNetEncoder if W.is_efficientnet(arch) else HipEncoder)
+           else EfficientNetEncoder if W.is_efficientnet(arch) else BeitEncoder if W.is_beit(arch) else HipEncoder)
     return cls(arch, state_dict, img_size=img_size, precision=precision, device=device, call_size_invariant=call_size_invariant)
 
 
@@ -412,7 +424,8 @@ def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size
     Only the ``"timm"`` backend is implemented, with the architectures BASELINE.json names (resnet18, vit_small_patch16_224,
     vit_base_patch16_224), ``convnext_tiny`` and ``mobilenetv3_small_050`` (recommended by the reference README for
     ``--auto_model_timm``), ``swin_tiny_patch4_window7_224``, ``resnet34``, ``resnet50``, ``mobilenetv3_small_075``, ``mobilenetv3_small_100``,
-    ``mobilenetv3_large_100``, ``efficientnet_b0`` and ``tf_efficientnet_b0`` (the "hf" branch and XcitDinoEncoder are out
+    ``mobilenetv3_large_100``, ``efficientnet_b0``, ``tf_efficientnet_b0``, ``beit_base_patch16_224`` and ``beitv2_base_patch16_224``
+    (the "hf" branch and XcitDinoEncoder are out
     of scope); anything else raises NotImplementedError exactly like the reference's ``else`` branch
     (encoders.py:93-95).
     ``precision`` / ``img_size`` / ``call_size_invariant`` (HipEncoder) are extensions with reference-compatible defaults.

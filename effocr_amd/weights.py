@@ -33,6 +33,14 @@ norm2,mlp.fc1,mlp.fc2}``, the patch merging ``layers.i.downsample.{norm,reductio
 ``strip_prefix``, and the derived buffers ``relative_position_index`` / ``attn_mask`` are dropped.  timm is not installed here either:
 the names could not be checked against timm itself; the architecture and the shapes are pinned against ``transformers.SwinModel``
 (tests/test_swin_host.py).
+
+BEiT (``beit_base_patch16_224`` / ``beitv2_base_patch16_224``) key names follow timm's ``beit.py`` as remembered (``cls_token``,
+``patch_embed.proj``, ``blocks.i.{gamma_1,gamma_2,norm1,attn.q_bias,attn.v_bias,attn.relative_position_bias_table,attn.qkv.weight,
+attn.proj,norm2,mlp.fc1,mlp.fc2}``, ``fc_norm``, classifier ``head``; no ``pos_embed`` and no ``attn.qkv.bias``) and are UNVERIFIED
+against a timm install.  The two names are the same module (they differ in their pre-training), so a checkpoint cannot tell them apart
+and ``infer_arch`` answers ``beit_base_patch16_224``.  The buffers ``attn.relative_position_index`` and ``attn.k_bias`` of older timm
+checkpoints are dropped by ``strip_prefix``.  The architecture and the shapes are pinned against ``transformers.BeitModel``
+(tests/test_beit_host.py).
 """
 from collections import OrderedDict
 import math
@@ -104,6 +112,13 @@ EFFICIENTNET_FEATURES = 1280          # conv_head width of EfficientNet-B0
 SWIN_CFG = {
     # name: (embed_dim, depths, heads, window) — timm swin_transformer.py; head dim 32 in every stage, mlp ratio 4, patch 4
     "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24), 7),
+}
+BEIT_CFG = {
+    # name: (embed_dim, depth, heads, mlp_ratio) — timm beit.py; patch 16, head dim 64, LayerNorm eps 1e-6, layer scale, a relative-position
+    # bias table per block, no absolute position embedding; the pooled output is fc_norm(mean of the patch tokens)
+    "beit_base_patch16_224": (768, 12, 12, 4),
+    "beitv2_base_patch16_224": (768, 12, 12, 4),
+    "beit_tiny_test": (128, 2, 2, 4),         # miniature used only by fast tests
 }
 MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
 MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
@@ -218,11 +233,33 @@ def embed_dim(arch):
         return SWIN_CFG[arch][0] * 8
     if arch in EFFICIENTNET_CFG:
         return EFFICIENTNET_FEATURES
+    if arch in BEIT_CFG:
+        return BEIT_CFG[arch][0]
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
 def is_swin(arch):
     return arch in SWIN_CFG
+
+
+def is_beit(arch):
+    """beit_base_patch16_224 / beitv2_base_patch16_224 (and the miniature beit_tiny_test): the encoders that run on libeffocr_beit.so."""
+    return arch in BEIT_CFG
+
+
+def beit_relative_position_index(W):
+    """[T, T] int64 index into a BEiT bias table of (2W-1)^2 + 3 rows for a W x W patch grid, T = W^2 + 1 tokens (token 0 = cls, token
+    1 + y W + x = patch (y, x)); entry [i, j] belongs to query i and key j.  Patch pairs: (y_i - y_j + W-1)(2W-1) + (x_i - x_j + W-1);
+    row 0 (cls -> any): (2W-1)^2; column 0 (any -> cls): (2W-1)^2 + 1; [0, 0]: (2W-1)^2 + 2."""
+    n = (2 * W - 1) ** 2
+    yy, xx = torch.meshgrid(torch.arange(W), torch.arange(W), indexing="ij")
+    y, x = yy.flatten(), xx.flatten()
+    idx = torch.empty(W * W + 1, W * W + 1, dtype=torch.long)
+    idx[1:, 1:] = (y[:, None] - y[None, :] + W - 1) * (2 * W - 1) + (x[:, None] - x[None, :] + W - 1)
+    idx[0, :] = n
+    idx[:, 0] = n + 1
+    idx[0, 0] = n + 2
+    return idx
 
 
 def resnet_expansion(arch):
@@ -245,9 +282,11 @@ def is_convnext(arch):
 # mobilenetv3 conv_head + hard-swish.
 # efficientnet_b0 / tf_efficientnet_b0: the global average pool of SiLU(bn2(conv_head)).
 # swin_tiny_patch4_window7_224: the mean of the final norm's tokens (timm >= 0.9 names the head head.fc; strip_prefix renames timm < 0.9's head).
+# beit_base_patch16_224 / beitv2_base_patch16_224: fc_norm of the mean of the patch tokens.
 HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bias"),
              "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias"),
-             "swin": ("head.fc.weight", "head.fc.bias"), "efficientnet": ("classifier.weight", "classifier.bias")}
+             "swin": ("head.fc.weight", "head.fc.bias"), "efficientnet": ("classifier.weight", "classifier.bias"),
+             "beit": ("head.weight", "head.bias")}
 
 
 def _family(arch):
@@ -263,6 +302,8 @@ def _family(arch):
         return "swin"
     if arch in EFFICIENTNET_CFG:
         return "efficientnet"
+    if arch in BEIT_CFG:
+        return "beit"
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -383,7 +424,43 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _swin_shapes(arch)
     if arch in EFFICIENTNET_CFG:
         return _efficientnet_shapes(arch)
+    if arch in BEIT_CFG:
+        return _beit_shapes(arch, img_size)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _beit_shapes(arch, img_size):
+    """timm's state-dict order (a module's own parameters before its children's: the layer scales open a block; q_bias, v_bias and the
+    bias table open its attention).  The table's length follows from the patch grid: (2 img_size/16 - 1)^2 + 3."""
+    D, depth, heads, r = BEIT_CFG[arch]
+    if img_size % PATCH or not PATCH <= img_size <= 224:
+        raise ValueError(f"{arch}: img_size must be a multiple of {PATCH} from {PATCH} to 224, got {img_size}")
+    entries = (2 * (img_size // PATCH) - 1) ** 2 + 3
+    s = OrderedDict()
+    s["cls_token"] = (1, 1, D)
+    s["patch_embed.proj.weight"] = (D, 3, PATCH, PATCH)
+    s["patch_embed.proj.bias"] = (D,)
+    for i in range(depth):
+        p = f"blocks.{i}."
+        s[p + "gamma_1"] = (D,)
+        s[p + "gamma_2"] = (D,)
+        s[p + "norm1.weight"] = (D,)
+        s[p + "norm1.bias"] = (D,)
+        s[p + "attn.q_bias"] = (D,)
+        s[p + "attn.v_bias"] = (D,)
+        s[p + "attn.relative_position_bias_table"] = (entries, heads)
+        s[p + "attn.qkv.weight"] = (3 * D, D)
+        s[p + "attn.proj.weight"] = (D, D)
+        s[p + "attn.proj.bias"] = (D,)
+        s[p + "norm2.weight"] = (D,)
+        s[p + "norm2.bias"] = (D,)
+        s[p + "mlp.fc1.weight"] = (r * D, D)
+        s[p + "mlp.fc1.bias"] = (r * D,)
+        s[p + "mlp.fc2.weight"] = (D, r * D)
+        s[p + "mlp.fc2.bias"] = (D,)
+    s["fc_norm.weight"] = (D,)
+    s["fc_norm.bias"] = (D,)
+    return s
 
 
 def _swin_shapes(arch):
@@ -546,6 +623,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_swin(arch, seed, img_size, scale)
     if is_resnet_lib(arch):
         return _init_resnet(arch, seed, img_size, scale)
+    if arch in BEIT_CFG:
+        return _init_beit(arch, seed, img_size, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -699,6 +778,41 @@ def _init_swin(arch, seed, img_size, scale):
     return sd
 
 
+def _init_beit(arch, seed, img_size, scale):
+    """BEiT seeded init from a CPU Philox generator of its own.  Both scales set the layer scales gamma_1 / gamma_2 to 0.1 (timm's
+    init_values for the base models) and draw nonzero bias tables and biases, so that no term of the forward is switched off:
+    scale="timm": trunc_normal(0.02) linears, patch conv and cls token, LayerNorms at identity, bias tables and biases N(0, 0.02);
+    scale="unit": fan-in-scaled linears and patch conv, cls token N(0, 0.5), LayerNorm gains U(0.5, 1.5), biases N(0, 0.1) and bias
+    tables N(0, 1) — a relative-position term as large as the scores, so a wrong index shows."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x62656974) % (1 << 63))
+    sd = OrderedDict()
+
+    def randn(shape, std):
+        return torch.randn(shape, generator=g, dtype=torch.float32) * std
+
+    for k, shp in param_shapes(arch, img_size).items():
+        leaf = k.rsplit(".", 1)[-1]
+        is_ln = "norm" in k
+        if leaf in ("gamma_1", "gamma_2"):
+            v = torch.full(shp, 0.1)
+        elif leaf == "relative_position_bias_table":
+            v = randn(shp, 0.02 if scale == "timm" else 1.0)
+        elif k == "cls_token":
+            v = randn(shp, 0.02).clamp_(-0.04, 0.04) if scale == "timm" else randn(shp, 0.5)
+        elif len(shp) == 1:
+            if scale == "timm":
+                v = torch.ones(shp) if (leaf == "weight" and is_ln) else (torch.zeros(shp) if is_ln else randn(shp, 0.02))
+            else:
+                v = torch.rand(shp, generator=g) + 0.5 if (leaf == "weight" and is_ln) else randn(shp, 0.1)
+        elif scale == "timm":
+            v = randn(shp, 0.02).clamp_(-0.04, 0.04)
+        else:
+            v = randn(shp, 1.0 / math.sqrt(math.prod(shp[1:])))
+        sd[k] = v.contiguous()
+    return sd
+
+
 def _init_resnet(arch, seed, img_size, scale):
     """resnet34 / resnet50 from a CPU Philox generator of their own (resnet18 keeps the generic stream of init_state_dict).
     Convolutions are kaiming-normal (std sqrt(2 / fan_in)), as timm's.  scale="timm": BN at identity, with the last BN of every residual
@@ -761,11 +875,16 @@ def infer_num_classes(sd):
 
 def strip_prefix(sd, prefix="net."):
     """models/encoders.py:60 keeps the timm module as ``self.net`` -> keys ``net.<timm key>``.  A Swin state dict also comes out in
-    timm >= 0.9's layout (swin_canonical); every other state dict only loses the prefix."""
+    timm >= 0.9's layout (swin_canonical) and a BEiT state dict without its derived buffers; every other state dict only loses the prefix."""
     keys = list(sd.keys())
     if keys and all(k.startswith(prefix) for k in keys):
         sd = OrderedDict((k[len(prefix):], v) for k, v in sd.items())
-    return swin_canonical(sd) if "layers.0.blocks.0.attn.relative_position_bias_table" in sd else OrderedDict(sd)
+    if "layers.0.blocks.0.attn.relative_position_bias_table" in sd:
+        return swin_canonical(sd)
+    if "blocks.0.attn.relative_position_bias_table" in sd:
+        # BEiT: the derived buffers of older timm checkpoints are dropped (the kernels compute the index from the geometry; k_bias is zeros)
+        return OrderedDict((k, v) for k, v in sd.items() if not k.endswith((".attn.relative_position_index", ".attn.k_bias")))
+    return OrderedDict(sd)
 
 
 _SWIN_OLD_DOWNSAMPLE = re.compile(r"^layers\.(\d+)\.downsample\.")
@@ -816,6 +935,15 @@ def save_checkpoint(sd, path, prefix="net."):
         torch.save(out, path)
 
 
+def beit_img_size(sd):
+    """Crop size a BEiT checkpoint was built for, from the length (2W-1)^2 + 3 of its bias tables (W = img_size / 16 patches per side)."""
+    n = int(strip_prefix(sd)["blocks.0.attn.relative_position_bias_table"].shape[0])
+    w2 = math.isqrt(max(n - 3, 0))
+    if n < 4 or w2 * w2 != n - 3 or w2 % 2 == 0 or (w2 + 1) // 2 > 224 // PATCH:
+        raise ValueError(f"unsupported BEiT: a relative_position_bias_table of {n} rows is not (2W-1)^2 + 3 for a patch grid W <= 14")
+    return (w2 + 1) // 2 * PATCH
+
+
 def infer_arch(sd):
     """Guess the architecture of a checkpoint from its parameter shapes."""
     sd = strip_prefix(sd)
@@ -834,6 +962,18 @@ def infer_arch(sd):
         for name, (d, dep, _, _) in VIT_CFG.items():
             if d == D and dep == depth:
                 return name
+    if ("cls_token" in sd and "blocks.0.attn.relative_position_bias_table" in sd and "blocks.0.gamma_1" in sd
+            and "fc_norm.weight" in sd):
+        # BEiT (no pos_embed: the ViT branch above did not take it).  beitv2_base_patch16_224 has the same keys and shapes and must be
+        # named by the caller
+        img = beit_img_size(sd)
+        D = int(sd["cls_token"].shape[-1])
+        depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        for name, (d, dep, _, _) in BEIT_CFG.items():
+            if d == D and dep == depth:
+                check_state_dict(name, sd, img)
+                return name
+        raise ValueError(f"unsupported BEiT: width {D}, depth {depth} (supported: base, width 768, depth 12)")
     if "stem.0.weight" in sd and any(k.startswith("stages.3.blocks.") for k in sd):
         depths = tuple(1 + max((int(k.split(".")[3]) for k in sd if k.startswith(f"stages.{i}.blocks.")), default=-1)
                        for i in range(4))
