@@ -280,11 +280,26 @@ def resnet_lib():
 # activations in HBM between blocks).
 MNV3_SO_PATH = os.path.join(_HERE, "libeffocr_mnv3.so")
 MNV3_ABI_VERSION = 1     # == EFFOCR_MNV3_ABI_VERSION of include/effocr_mnv3.h
-MNV3_EXPORTS = tuple(sorted(_encoder_signatures("mnv3")))
+
+
+def _mnv3_signatures():
+    c = ctypes
+    vp, i32, i64 = c.c_void_p, c.c_int, c.c_int64
+    sig = _encoder_signatures("mnv3")
+    sig["effocr_mnv3_op_stem"] = (i32, [vp, i32, i32, vp, vp, vp, vp])                          # test entry points
+    sig["effocr_mnv3_op_dw"] = (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp])
+    sig["effocr_mnv3_op_se_gate"] = (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp])
+    sig["effocr_mnv3_op_pw"] = (i32, [i32, vp, i64, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp])
+    sig["effocr_mnv3_op_pool"] = (i32, [vp, i32, i32, i32, vp, vp])
+    sig["effocr_mnv3_op_finish"] = (i32, [vp, i32, i32, i32, vp, vp])
+    return sig
+
+
+MNV3_EXPORTS = tuple(sorted(_mnv3_signatures()))
 
 
 def mnv3_lib():
-    return _load_family(MNV3_SO_PATH, "mnv3", MNV3_ABI_VERSION, _encoder_signatures("mnv3"), "MobileNetV3 encoder")
+    return _load_family(MNV3_SO_PATH, "mnv3", MNV3_ABI_VERSION, _mnv3_signatures(), "MobileNetV3 encoder")
 
 
 # libeffocr_effnet.so (include/effocr_effnet.h): the EfficientNet-B0 encoders efficientnet_b0 / tf_efficientnet_b0 (its own stem,

@@ -18,10 +18,14 @@
 namespace effocr {
 namespace {
 
+// NaN-propagating maximum / minimum (IEEE 754-2019; v_maximum3_f32 / v_minimum3_f32), as torch's relu, hardswish and hardsigmoid: fmaxf and
+// fminf return the operand that is not NaN, which turned a NaN crop into a finite embedding (DESIGN.md "NaN semantics")
+__device__ __forceinline__ float mg_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float mg_min(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float mg_hsig(float x) { return mg_min(mg_max(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
 __device__ __forceinline__ float mg_act(float x, int a) {
-  return a == MG_ACT_RELU ? fmaxf(x, 0.0f) : a == MG_ACT_HS ? x * (fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f) : a == MG_ACT_SILU ? silu_fast(x) : x;
+  return a == MG_ACT_RELU ? mg_max(x, 0.0f) : a == MG_ACT_HS ? x * mg_hsig(x) : a == MG_ACT_SILU ? silu_fast(x) : x;
 }
-__device__ __forceinline__ float mg_hsig(float x) { return fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
 
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(256) void mg_se_gate_kernel(const float* __restrict
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s = fmaf(wr[(int64_t)j * C + c], mean[c], s);
     s = mg_wave_sum(s);
-    if (lane == 0) hid[j] = fmaxf(s + br[j], 0.f);
+    if (lane == 0) hid[j] = mg_max(s + br[j], 0.f);
   }
   __syncthreads();
   for (int c = wave; c < C; c += 4) {                    // one wave per gate
@@ -255,7 +259,8 @@ __global__ __launch_bounds__(256) void mg_finish_kernel(float* __restrict__ emb,
     sq = mg_wave_sum(sq);
     if (lane == 0) ss[wave] = sq;
     __syncthreads();
-    const float den = fmaxf(sqrtf((ss[0] + ss[1]) + (ss[2] + ss[3])), 1e-12f);   // F.normalize: x / max(||x||, eps)
+    const float nr = sqrtf((ss[0] + ss[1]) + (ss[2] + ss[3]));
+    const float den = nr < 1e-12f ? 1e-12f : nr;         // F.normalize: x / max(||x||, eps); a NaN norm stays NaN, as torch's clamp_min
     for (int d = tid; d < D; d += 256) e[d] = e[d] / den;
   }
   if (bad) atomicOr(status, 1);

@@ -287,3 +287,56 @@ MNV3_API int effocr_mnv3_forward(effocr_mnv3_t* enc, const float* x_dev, int bat
 MNV3_API int effocr_mnv3_check_status(const effocr_mnv3_t* enc, const void* workspace_dev, void* stream) {   // MgWs::status = offset 0
   return enc_check_status("mnv3", enc, workspace_dev, stream, MBCONV_FP16_OVERFLOW);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// TEST ENTRY POINTS (include/effocr_mnv3.h): thin wrappers over mnv3g.hpp's launchers with their layouts, every argument checked before
+// the launch.  No product code calls them.
+MNV3_API int effocr_mnv3_op_stem(const float* x_dev, int batch, int img_size, const float* w_dev, const float* b_dev, float* out_dev,
+                                 void* stream) {
+  if (!x_dev || !w_dev || !b_dev || !out_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_stem: NULL argument");
+  if (batch <= 0 || img_size <= 0) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_stem: bad geometry");
+  if (img_size % 2) return fail(EFFOCR_MNV3_EUNSUPPORTED, "mnv3_op_stem: odd img_size");
+  return mg_stem(x_dev, batch, img_size, w_dev, b_dev, out_dev, S(stream));
+}
+
+MNV3_API int effocr_mnv3_op_dw(const float* in_dev, int batch, int in_size, int channels, int kernel, int stride, const float* w_dev,
+                               const float* b_dev, int act, float* out_dev, void* stream) {
+  if (!in_dev || !w_dev || !b_dev || !out_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_dw: NULL argument");
+  if (batch <= 0 || in_size <= 0 || channels <= 0 || act < MG_ACT_NONE || act > MG_ACT_SILU) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_dw: bad geometry");
+  if (channels % 4 || (kernel != 3 && kernel != 5) || (stride != 1 && stride != 2))
+    return fail(EFFOCR_MNV3_EUNSUPPORTED, "mnv3_op_dw: channels % 4 == 0, kernel 3 or 5, stride 1 or 2");
+  return mg_dw(in_dev, batch, in_size, channels, kernel, stride, w_dev, b_dev, act, out_dev, out_size(in_size, stride), S(stream));
+}
+
+MNV3_API int effocr_mnv3_op_se_gate(const float* t_dev, int batch, int pixels, int channels, int se_width, const float* reduce_w_dev,
+                                    const float* reduce_b_dev, const float* expand_w_dev, const float* expand_b_dev, float* gate_dev,
+                                    void* stream) {
+  if (!t_dev || !reduce_w_dev || !reduce_b_dev || !expand_w_dev || !expand_b_dev || !gate_dev)
+    return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_se_gate: NULL argument");
+  if (batch <= 0 || pixels <= 0 || channels <= 0 || se_width <= 0) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_se_gate: bad geometry");
+  // (mg_se_gate refuses channels > 1024 and se_width > 256: its LDS tables)
+  return mg_se_gate(t_dev, batch, pixels, channels, se_width, reduce_w_dev, reduce_b_dev, expand_w_dev, expand_b_dev, gate_dev, S(stream));
+}
+
+MNV3_API int effocr_mnv3_op_pw(int precision, const float* a_dev, int64_t rows, int k, const void* w_dev, int n, const float* bias_dev,
+                               const float* gate_dev, int pixels_per_crop, int act, const float* resid_dev, float* out_dev, void* stream) {
+  if (!a_dev || !w_dev || !bias_dev || !out_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_pw: NULL argument");
+  if (precision < 0 || precision > 2) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_pw: unknown precision");
+  if (rows <= 0 || k <= 0 || n <= 0 || pixels_per_crop <= 0 || act < MG_ACT_NONE || act > MG_ACT_SILU)
+    return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_pw: bad geometry");
+  if (k % 4 || n % 4) return fail(EFFOCR_MNV3_EUNSUPPORTED, "mnv3_op_pw: K and N must be multiples of 4");
+  if (n > 65535 * 64) return fail(EFFOCR_MNV3_EUNSUPPORTED, "mnv3_op_pw: N beyond the grid");
+  return mg_pw(precision, a_dev, rows, k, w_dev, n, bias_dev, gate_dev, pixels_per_crop, act, resid_dev, out_dev, S(stream));
+}
+
+MNV3_API int effocr_mnv3_op_pool(const float* t_dev, int batch, int pixels, int channels, float* out_dev, void* stream) {
+  if (!t_dev || !out_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_pool: NULL argument");
+  if (batch <= 0 || pixels <= 0 || channels <= 0) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_pool: bad geometry");
+  return mg_pool(t_dev, batch, pixels, channels, out_dev, S(stream));
+}
+
+MNV3_API int effocr_mnv3_op_finish(float* emb_dev, int batch, int dim, int l2_normalize, int* status_dev, void* stream) {
+  if (!emb_dev || !status_dev) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_finish: NULL argument");
+  if (batch <= 0 || dim <= 0) return fail(EFFOCR_MNV3_EINVAL, "mnv3_op_finish: bad geometry");
+  return mg_finish(emb_dev, batch, dim, l2_normalize, status_dev, S(stream));
+}

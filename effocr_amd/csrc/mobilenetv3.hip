@@ -20,9 +20,13 @@ namespace {
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_HS = 2 };
 
-__device__ __forceinline__ float hsig(float x) { return fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
+// NaN-propagating maximum / minimum (IEEE 754-2019; v_maximum3_f32 / v_minimum3_f32), as torch's relu, hardswish and hardsigmoid: fmaxf and
+// fminf return the operand that is not NaN, which turned a NaN crop into a finite embedding (DESIGN.md "NaN semantics")
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float min_nan(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float hsig(float x) { return min_nan(max_nan(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
 __device__ __forceinline__ float act_f(float x, int a) {
-  return a == ACT_RELU ? fmaxf(x, 0.0f) : a == ACT_HS ? x * (fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f) : x;
+  return a == ACT_RELU ? max_nan(x, 0.0f) : a == ACT_HS ? x * hsig(x) : x;
 }
 
 template <typename T> __device__ __forceinline__ const T* WP(const char* wb, uint32_t off) { return reinterpret_cast<const T*>(wb + off); }
@@ -125,7 +129,7 @@ __device__ __forceinline__ void se_gate(const float* m, int C, int R, const char
   for (int j = threadIdx.x; j < R; j += blockDim.x) {
     float a = br[j];
     for (int c = 0; c < C; ++c) a = fmaf(wr[j * C + c], m[c], a);
-    h[j] = fmaxf(a, 0.f);
+    h[j] = max_nan(a, 0.f);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
@@ -234,7 +238,7 @@ __global__ __launch_bounds__(256) void mnv3_stage1_kernel(const float* __restric
   {
     const float* bb = WP<float>(wb, b1.pw.b);
     pw_lds<TW>(r1, 8, R21 * R21, 8, WP<TW>(wb, b1.pw.w), 40, nullptr,
-               [&](int p, int n, float a) { r2[p * 40 + n] = in4(p) ? fmaxf(a + bb[n], 0.f) : 0.f; });
+               [&](int p, int n, float a) { r2[p * 40 + n] = in4(p) ? max_nan(a + bb[n], 0.f) : 0.f; });
   }
   dw_lds(r2, 40, R21, R21, 40, WP<float>(wb, b1.dw.w), WP<float>(wb, b1.dw.b), 3, 2, 0, ACT_RELU, r0, 40, R10, R10);
   {
@@ -245,7 +249,7 @@ __global__ __launch_bounds__(256) void mnv3_stage1_kernel(const float* __restric
   {
     const float* bb = WP<float>(wb, b2.pw.b);
     pw_lds<TW>(r1, 16, R10 * R10, 16, WP<TW>(wb, b2.pw.w), 56, nullptr,
-               [&](int p, int n, float a) { r2[p * 56 + n] = in8(p) ? fmaxf(a + bb[n], 0.f) : 0.f; });
+               [&](int p, int n, float a) { r2[p * 56 + n] = in8(p) ? max_nan(a + bb[n], 0.f) : 0.f; });
   }
   dw_lds(r2, 56, R10, R10, 56, WP<float>(wb, b2.dw.w), WP<float>(wb, b2.dw.b), 3, 1, 0, ACT_RELU, r0, 56, MNV_T2, MNV_T2);
   {
@@ -393,7 +397,8 @@ __global__ __launch_bounds__(256) void mnv3_head_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float n2 = (ss[0][kq + i] + ss[1][kq + i]) + (ss[2][kq + i] + ss[3][kq + i]);
-      sq[i] = fmaxf(sqrtf(n2), 1e-12f);                  // F.normalize: x / max(||x||, eps)
+      const float nr = sqrtf(n2);
+      sq[i] = nr < 1e-12f ? 1e-12f : nr;                 // F.normalize: x / max(||x||, eps); a NaN norm stays NaN, as torch's clamp_min
     }
   }
   bool bad = false;

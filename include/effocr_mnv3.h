@@ -89,6 +89,30 @@ int effocr_mnv3_forward(effocr_mnv3_t* enc, const float* x_dev, int batch, float
  * workspace since the last check produced a non-finite embedding, else 0. */
 int effocr_mnv3_check_status(const effocr_mnv3_t* enc, const void* workspace_dev, void* stream);
 
+/* TEST ENTRY POINTS: the six kernels of the forward, one launch each, on caller-made DEVICE tensors (tests/test_gpu_mobilenetv3_ops.py
+ * compares each with a float64 restatement).  All tensors fp32 and channels-last unless stated; act = 0 none, 1 ReLU, 2 hard-swish,
+ * 3 SiLU.  Every argument is checked before the launch: a NULL pointer or a non-positive size is EFFOCR_MNV3_EINVAL, a geometry the
+ * kernel does not implement EFFOCR_MNV3_EUNSUPPORTED.  No product code calls them.
+ *   op_stem     x [batch,3,S,S] NCHW (S even) -> out [batch,S/2,S/2,16] = hardswish(conv3x3/2 pad 1 + b); w [27][16], row (ci*3+ky)*3+kx
+ *   op_dw       in [batch,H,H,C] -> out [batch,Ho,Ho,C] = act(depthwise k x k, pad k/2 + b), Ho = (H-1)/stride+1; w [k*k][C], row ky*k+kx;
+ *               C % 4 == 0, k 3 or 5, stride 1 or 2
+ *   op_se_gate  t [batch,pixels,C] -> gate [batch,C] = hardsigmoid(expand_w . relu(reduce_w . mean(t) + reduce_b) + expand_b);
+ *               reduce_w [R][C], expand_w [C][R]; C <= 1024, R <= 256
+ *   op_pw       out [rows,N] = act((a [rows,K] * gate[row / pixels_per_crop][k]) . w^T + bias) (+ resid [rows,N]); gate [crops,K] and resid
+ *               may be NULL; K % 4 == 0, N % 4 == 0.  w as the forward reads it: precision 2 (fp32): [N][K] fp32; 0 / 1 (bf16 / f16):
+ *               [16 ceil(N/16)][Kp] of that type, Kp = K rounded up to 16, zero padded
+ *   op_pool     t [batch,pixels,C] -> out [batch,C], the mean over the pixels
+ *   op_finish   emb [batch,D] in place: F.normalize when l2_normalize != 0; ORs 1 into *status_dev (int32) if a value read was non-finite */
+int effocr_mnv3_op_stem(const float* x_dev, int batch, int img_size, const float* w_dev, const float* b_dev, float* out_dev, void* stream);
+int effocr_mnv3_op_dw(const float* in_dev, int batch, int in_size, int channels, int kernel, int stride, const float* w_dev,
+                      const float* b_dev, int act, float* out_dev, void* stream);
+int effocr_mnv3_op_se_gate(const float* t_dev, int batch, int pixels, int channels, int se_width, const float* reduce_w_dev,
+                           const float* reduce_b_dev, const float* expand_w_dev, const float* expand_b_dev, float* gate_dev, void* stream);
+int effocr_mnv3_op_pw(int precision, const float* a_dev, int64_t rows, int k, const void* w_dev, int n, const float* bias_dev,
+                      const float* gate_dev, int pixels_per_crop, int act, const float* resid_dev, float* out_dev, void* stream);
+int effocr_mnv3_op_pool(const float* t_dev, int batch, int pixels, int channels, float* out_dev, void* stream);
+int effocr_mnv3_op_finish(float* emb_dev, int batch, int dim, int l2_normalize, int* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

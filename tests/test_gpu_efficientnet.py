@@ -299,6 +299,40 @@ def test_status_reports_nonfinite_weight(dev, prec):
     enc.check_status()                                     # the next clean forward is OK
 
 
+@functools.lru_cache(maxsize=None)
+def _nonfinite_reference(arch, bad):
+    """Four 64^2 crops with one non-finite pixel in crop 2, through the float64 restatement on the signal checkpoint: row 2 is NaN in
+    every column, the other rows are those of the clean crops bit for bit."""
+    x = _crops(4, 64, 8)
+    xb = x.clone()
+    xb[2, 1, 29, 41] = bad
+    sd = _signal_sd(arch, 64)
+    clean, ref = efficientnet_forward(arch, sd, x.double()), efficientnet_forward(arch, sd, xb.double())
+    assert bool(ref[2].isnan().all()) and torch.equal(ref[[0, 1, 3]], clean[[0, 1, 3]]) and bool(torch.isfinite(clean).all())
+    return x, xb
+
+
+@pytest.mark.parametrize("prec", ["fp16", "bf16", "fp32"])
+@pytest.mark.parametrize("arch", ARCHS)
+def test_status_reports_nonfinite_input(dev, arch, prec):
+    """A NaN pixel, then an inf pixel, in crop 2 of 4 (data, not a fault): check_status raises code -6, row 2 of the embedding is NaN in
+    every column as the restatement's, rows 0, 1 and 3 are bit-equal to the clean forward, and the word then reads clear — with and
+    without the fused normalisation (mg_finish, shared with the MobileNetV3 library)."""
+    enc = _engine(arch, dict(_signal_sd(arch, 64)), 64, prec, dev)
+    for bad in (float("nan"), float("inf")):
+        x, xb = _nonfinite_reference(arch, bad)
+        for normalize in (False, True):
+            clean = enc.forward(x.to(dev), normalize=normalize)
+            enc.check_status()
+            got = enc.forward(xb.to(dev), normalize=normalize)
+            with pytest.raises(_lib.EffOCRHipError, match="code -6"):
+                enc.check_status()
+            enc.check_status()                                 # read-and-clear: the word is clear again
+            nan_cols = int(got[2].isnan().sum().item())
+            assert nan_cols == got.shape[1], f"{arch} {prec} {bad} normalize={normalize}: row 2 has {nan_cols} NaN columns of {got.shape[1]}"
+            assert torch.equal(got[[0, 1, 3]], clean[[0, 1, 3]])
+
+
 def test_workspace_too_small_and_16bit_crops_are_refused(dev):
     arch = "efficientnet_b0"
     enc = _engine(arch, _sd(arch, 6, 64), 64, "fp16", dev)

@@ -12,7 +12,9 @@ import torch.nn.functional as F
 
 from effocr_amd import _lib
 from effocr_amd import weights as W
+from tests import mobilenetv3_family_ref as MR
 from tests.mobilenetv3_family_ref import mobilenetv3_family_forward
+from tests.mobilenetv3_ref import mobilenetv3_forward
 
 ARCHS = ["mobilenetv3_small_075", "mobilenetv3_small_100", "mobilenetv3_large_100"]
 LARGE = "mobilenetv3_large_100"
@@ -228,7 +230,7 @@ def _create(arch, img=224, prec=1):
 
 def test_every_symbol_resolves():
     L = _lib.mnv3_lib()
-    assert len(_lib.MNV3_EXPORTS) == 15 and all(n.startswith("effocr_mnv3_") for n in _lib.MNV3_EXPORTS)
+    assert len(_lib.MNV3_EXPORTS) == 21 and all(n.startswith("effocr_mnv3_") for n in _lib.MNV3_EXPORTS)
     for name in _lib.MNV3_EXPORTS:
         assert getattr(L, name) is not None
     assert L.effocr_mnv3_abi_version() == _lib.MNV3_ABI_VERSION
@@ -292,3 +294,39 @@ def test_c_create_rejects_other_archs_and_product_library_unchanged():
     h = ctypes.c_void_p()
     for a in ARCHS:
         assert lib.effocr_encoder_create(a.encode(), 224, 1, ctypes.byref(h)) == -2      # the product library goes on refusing them
+
+
+# ---------------------------------------------------------------------------------------------------- the restatement's round_pw path, the signal checkpoint
+@pytest.mark.parametrize("arch", ARCHS + ["mobilenetv3_small_050"])
+def test_round_pw_path_against_plain(arch):
+    """The restatement's round_pw path (the GPU tests' e_w) folds BN into the weights: with no rounding to speak of it gives the plain
+    path's result, with bf16 it does not.  The plain path itself is untouched: mobilenetv3_small_050 through it is bit-identical to
+    tests/mobilenetv3_ref.py, the same sequence of operations written out a second time."""
+    sd = W.init_state_dict(arch, seed=11, img_size=64, scale="timm")
+    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(3)).double()
+    a = mobilenetv3_family_forward(arch, sd, x)
+    assert torch.equal(a, mobilenetv3_family_forward(arch, sd, x, round_pw=None))
+    if arch == "mobilenetv3_small_050":
+        assert torch.equal(a, mobilenetv3_forward(arch, sd, x))
+    b = mobilenetv3_family_forward(arch, sd, x, round_pw=torch.float32)
+    c = mobilenetv3_family_forward(arch, sd, x, round_pw=torch.bfloat16)
+    rel = lambda u, v: ((u - v).abs().max() / v.abs().max()).item()
+    assert rel(b, a) < 2e-6 and 1e-4 < rel(c, a) < 5e-2
+
+
+@pytest.mark.parametrize("img", MR.SIGNAL_IMGS + (224,))
+@pytest.mark.parametrize("arch", ARCHS + ["mobilenetv3_small_050"])
+def test_signal_checkpoint_depends_on_the_crop(arch, img):
+    """The premise of the GPU tests' crop-dependent parity, from the reference alone: all-zero crops and transposed crops each move the
+    float64 embedding of the signal checkpoint by more than 0.1 of its norm, and a float32 run of the restatement stays within 3e-6 of
+    float64 (the checkpoint does not amplify rounding, so the fp32 mode's 1e-5 stands).  224^2: the batch-invariance cases that use it."""
+    if img == 224 and arch not in ("mobilenetv3_small_050", "mobilenetv3_small_100"):
+        return
+    B = 2 if img == 224 else MR.SIGNAL_B
+    ref, d_zero, d_transposed = MR.signal_reference(arch, img, None, B)
+    f32 = mobilenetv3_family_forward(arch, MR.signal_sd(arch, img), MR.signal_crops(img, B))
+    e32 = ((f32 - ref).abs().max() / ref.abs().max()).item()
+    print(f"{arch} {img}^2 gain {MR.SIGNAL_GAIN[arch]}: zero crops {d_zero:.2f}, transposed {d_transposed:.2f}, float32 vs float64 {e32:.1e}")
+    assert d_zero > 0.1 and d_transposed > 0.1 and e32 < 3e-6
+    unit = W.init_state_dict(arch, seed=7, img_size=img)
+    assert all(torch.equal(v, unit[k]) for k, v in MR.signal_sd(arch, img).items() if v.dim() != 4 or ".se." in k)
