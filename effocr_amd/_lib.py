@@ -258,11 +258,24 @@ def _encoder_signatures(prefix):
     }.items()}
 
 
-SWIN_EXPORTS = tuple(sorted(_encoder_signatures("swin")))
+def _swin_signatures():
+    c = ctypes
+    vp, i32, i64 = c.c_void_p, c.c_int, c.c_int64
+    sig = _encoder_signatures("swin")
+    sig["effocr_swin_op_stem"] = (i32, [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp])             # test entry points
+    sig["effocr_swin_op_layernorm"] = (i32, [i32, vp, i64, i32, i32, vp, vp, vp, vp])
+    sig["effocr_swin_op_merge"] = (i32, [i32, vp, i32, i32, i32, i32, vp, vp, vp, vp])
+    sig["effocr_swin_op_window_attention"] = (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp])
+    sig["effocr_swin_op_head"] = (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp])
+    sig["effocr_swin_op_linear"] = (i32, [i32, i32, vp, vp, vp, vp, vp, i64, i32, i32, vp])
+    return sig
+
+
+SWIN_EXPORTS = tuple(sorted(_swin_signatures()))
 
 
 def swin_lib():
-    return _load_family(SWIN_SO_PATH, "swin", SWIN_ABI_VERSION, _encoder_signatures("swin"), "Swin encoder")
+    return _load_family(SWIN_SO_PATH, "swin", SWIN_ABI_VERSION, _swin_signatures(), "Swin encoder")
 
 
 # libeffocr_resnet.so (include/effocr_resnet.h): the ResNet-34 / ResNet-50 encoders (it carries its own copy of resnet18's fp32

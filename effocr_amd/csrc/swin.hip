@@ -323,7 +323,7 @@ int swin_layernorm(int prec, const float* x, int64_t M, int C, int Cp, const flo
 
 int swin_merge(int prec, const float* x, int B, int H, int C, int Cp, const float* lnw, const float* lnb, float eps, void* out, hipStream_t s) {
   if (B <= 0) return EFFOCR_OK;
-  if (C % 32 || C > 384 || C > Cp || H % 2) return fail(EFFOCR_EUNSUPPORTED, "swin_merge: C must be a multiple of 32 (<= 384), H even");
+  if (C % 32 || C > 384 || C > Cp || Cp % 4 || H % 2) return fail(EFFOCR_EUNSUPPORTED, "swin_merge: C must be a multiple of 32 (<= 384), H even");
   const int segs = C >= 256 ? 1 : 256 / C;
   const int64_t M = (int64_t)B * (H / 2) * (H / 2);
   const dim3 grid((unsigned)((M + segs - 1) / segs)), block(segs * C);
@@ -355,7 +355,7 @@ int swin_window_attention(int prec, const void* qkv, int B, int H, int C, int Cp
 int swin_head(const float* x, int B, int HW, int C, int Cp, const float* lnw, const float* lnb, float eps, int l2norm, float* emb, int* status,
               hipStream_t s) {
   if (B <= 0) return EFFOCR_OK;
-  if (C % 128 || C > 1024 || C > Cp || HW <= 0) return fail(EFFOCR_EUNSUPPORTED, "swin_head: bad shape");
+  if (C % 128 || C > 1024 || C > Cp || Cp % 4 || HW <= 0) return fail(EFFOCR_EUNSUPPORTED, "swin_head: bad shape");
   hipLaunchKernelGGL(swin_head_kernel, dim3((unsigned)B), dim3(C / 4), 0, s, x, HW, C, Cp, lnw, lnb, eps, l2norm, emb, status);
   return check_launch("swin_head");
 }

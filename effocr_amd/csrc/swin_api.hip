@@ -171,6 +171,16 @@ int swin_chunk(const effocr_swin* e, int batch) {
   return c < batch ? c : batch;
 }
 
+// One linear of the forward, out [M][N] = epilogue(X [M][K] . W [N][K]^T + bias): dense rows (ldx = ldw = K, ldo = ldr = N), the kernel
+// chosen by (precision, N, K) alone.  resid (EPI_BIAS_RESID only) may be out itself: the forward adds into the residual stream in place.
+int swin_linear(int prec, int epi, const void* X, const void* W, const float* bias, const float* resid, void* out, int64_t M, int N, int K,
+                hipStream_t s) {
+  GemmArgs g{};
+  g.X = X; g.ldx = K; g.W = W; g.ldw = K; g.bias = bias; g.out = out; g.ldo = N; g.M = (int)M; g.N = N; g.K = K;
+  if (epi == EPI_BIAS_RESID) { g.resid = resid; g.ldr = N; }
+  return gemm2_supported(prec, N, K) ? gemm2_nt(prec, epi, g, s) : gemm_nt(prec, epi, g, s);
+}
+
 // One sub-batch: patch_embed -> 4 stages of [patch merging] + blocks (LN1 -> qkv -> window attention -> proj + residual; LN2 -> fc1 + GELU
 // -> fc2 + residual) -> head.  Every GEMM's kernel is chosen by (precision, N, K) alone and reduces K in a fixed order (no split-K):
 // a crop's embedding does not depend on B.
@@ -184,10 +194,7 @@ int swin_forward(const effocr_swin* e, const float* x, int B, float* emb, int l2
   int* status = reinterpret_cast<int*>(ws + w.status);
   int rc;
   auto lin = [&](const void* X, int K, size_t woff, size_t boff, void* out, int N, int epi, int64_t M) {
-    GemmArgs g{};
-    g.X = X; g.ldx = K; g.W = wb + woff; g.ldw = K; g.bias = F(boff); g.out = out; g.ldo = N; g.M = (int)M; g.N = N; g.K = K;
-    if (epi == EPI_BIAS_RESID) { g.resid = xs; g.ldr = N; }
-    return gemm2_supported(prec, N, K) ? gemm2_nt(prec, epi, g, s) : gemm_nt(prec, epi, g, s);
+    return swin_linear(prec, epi, X, wb + woff, F(boff), epi == EPI_BIAS_RESID ? xs : nullptr, out, M, N, K, s);
   };
   if ((rc = swin_stem(x, B, e->img, F(e->stemw), F(e->stemb), F(e->stemlnw), F(e->stemlnb), e->st[0].C, SWIN_EPS, xs, s))) return rc;
   for (int i = 0; i < 4; ++i) {
@@ -275,4 +282,77 @@ SWIN_API int effocr_swin_check_status(const effocr_swin_t* enc, const void* work
   return enc_check_status("swin", enc, workspace_dev, stream,
                           "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
                           "input was not finite; use precision bf16 or fp32 for this checkpoint");
+}
+
+// ---- test entry points (tests/test_gpu_swin_ops.py): one launcher each, arguments checked before any launch ----------------------
+#define SWIN_OP_PREC(name) if (precision < 0 || precision > 2) return fail(EFFOCR_SWIN_EINVAL, name ": unknown precision")
+
+SWIN_API int effocr_swin_op_stem(const float* x_dev, int batch, int img_size, const float* w_dev, const float* b_dev, const float* lnw_dev,
+                                 const float* lnb_dev, int channels, float* out_dev, void* stream) {
+  if (!x_dev || !w_dev || !b_dev || !lnw_dev || !lnb_dev || !out_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_stem: NULL argument");
+  if (batch <= 0 || img_size <= 0 || channels <= 0) return fail(EFFOCR_SWIN_EINVAL, "swin_op_stem: bad geometry");
+  if (img_size % 4 || channels > 128 || channels % 4)
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_stem: img_size % 4 == 0, channels % 4 == 0 and channels <= 128 required");
+  return swin_stem(x_dev, batch, img_size, w_dev, b_dev, lnw_dev, lnb_dev, channels, SWIN_EPS, out_dev, S(stream));
+}
+
+SWIN_API int effocr_swin_op_layernorm(int precision, const float* x_dev, int64_t rows, int channels, int padded_channels, const float* lnw_dev,
+                                      const float* lnb_dev, void* out_dev, void* stream) {
+  if (!x_dev || !lnw_dev || !lnb_dev || !out_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_layernorm: NULL argument");
+  SWIN_OP_PREC("swin_op_layernorm");
+  if (rows <= 0 || channels <= 0 || padded_channels <= 0) return fail(EFFOCR_SWIN_EINVAL, "swin_op_layernorm: bad geometry");
+  if (padded_channels % 128 || padded_channels > 1024 || channels > padded_channels || channels % 4)
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_layernorm: padded_channels % 128 == 0 (<= 1024), channels % 4 == 0 and channels <= "
+                                          "padded_channels required");
+  return swin_layernorm(precision, x_dev, rows, channels, padded_channels, lnw_dev, lnb_dev, SWIN_EPS, out_dev, S(stream));
+}
+
+SWIN_API int effocr_swin_op_merge(int precision, const float* x_dev, int batch, int map_size, int channels, int padded_channels,
+                                  const float* lnw_dev, const float* lnb_dev, void* out_dev, void* stream) {
+  if (!x_dev || !lnw_dev || !lnb_dev || !out_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_merge: NULL argument");
+  SWIN_OP_PREC("swin_op_merge");
+  if (batch <= 0 || map_size <= 0 || channels <= 0 || padded_channels <= 0) return fail(EFFOCR_SWIN_EINVAL, "swin_op_merge: bad geometry");
+  if (channels % 32 || channels > 384 || channels > padded_channels || padded_channels % 4 || map_size % 2)
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_merge: channels % 32 == 0 (<= 384, <= padded_channels), padded_channels % 4 == 0 and an "
+                                          "even map_size required");
+  return swin_merge(precision, x_dev, batch, map_size, channels, padded_channels, lnw_dev, lnb_dev, SWIN_EPS, out_dev, S(stream));
+}
+
+SWIN_API int effocr_swin_op_window_attention(int precision, const void* qkv_dev, int batch, int map_size, int channels, int padded_channels,
+                                             int shift, const float* table_dev, void* out_dev, void* stream) {
+  if (!qkv_dev || !table_dev || !out_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_window_attention: NULL argument");
+  SWIN_OP_PREC("swin_op_window_attention");
+  if (batch <= 0 || map_size <= 0 || channels <= 0 || padded_channels <= 0)
+    return fail(EFFOCR_SWIN_EINVAL, "swin_op_window_attention: bad geometry");
+  if (map_size % SWIN_WS || channels % 32 || channels > padded_channels || padded_channels % 8 || shift < 0 || shift >= SWIN_WS ||
+      (shift && map_size <= SWIN_WS))
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_window_attention: map_size % 7 == 0, channels % 32 == 0 (<= padded_channels), "
+                                          "padded_channels % 8 == 0 and 0 <= shift < 7 (0 for a single window) required");
+  if ((int64_t)batch * (map_size / SWIN_WS) * (map_size / SWIN_WS) * (channels / 32) >= (int64_t)1 << 31)
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_window_attention: more (crop, window, head) workgroups than a grid holds");
+  return swin_window_attention(precision, qkv_dev, batch, map_size, channels, padded_channels, shift, table_dev, out_dev, S(stream));
+}
+
+SWIN_API int effocr_swin_op_head(const float* x_dev, int batch, int tokens, int channels, int padded_channels, const float* lnw_dev,
+                                 const float* lnb_dev, int l2_normalize, float* emb_dev, int* status_dev, void* stream) {
+  if (!x_dev || !lnw_dev || !lnb_dev || !emb_dev || !status_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_head: NULL argument");
+  if (batch <= 0 || tokens <= 0 || channels <= 0 || padded_channels <= 0) return fail(EFFOCR_SWIN_EINVAL, "swin_op_head: bad geometry");
+  if (channels % 128 || channels > 1024 || channels > padded_channels || padded_channels % 4)
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_head: channels % 128 == 0 (<= 1024, <= padded_channels) and padded_channels % 4 == 0 "
+                                          "required");
+  return swin_head(x_dev, batch, tokens, channels, padded_channels, lnw_dev, lnb_dev, SWIN_EPS, l2_normalize, emb_dev, status_dev, S(stream));
+}
+
+SWIN_API int effocr_swin_op_linear(int precision, int epilogue, const void* x_dev, const void* w_dev, const float* bias_dev, const float* resid_dev,
+                                   void* out_dev, int64_t rows, int n, int k, void* stream) {
+  if (!x_dev || !w_dev || !bias_dev || !out_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_linear: NULL argument");
+  SWIN_OP_PREC("swin_op_linear");
+  if (epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_RESID && epilogue != EPI_BIAS_F32)
+    return fail(EFFOCR_SWIN_EINVAL, "swin_op_linear: unknown epilogue (0 bias, 1 bias + GELU, 2 bias + residual, 5 bias with fp32 output)");
+  if (epilogue == EPI_BIAS_RESID && !resid_dev) return fail(EFFOCR_SWIN_EINVAL, "swin_op_linear: NULL residual");
+  if (rows <= 0 || n <= 0 || k <= 0) return fail(EFFOCR_SWIN_EINVAL, "swin_op_linear: bad geometry");
+  if (n % 128 || (k * prec_esize(precision)) % 128)
+    return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_linear: n % 128 == 0 and rows of k elements a multiple of 128 bytes required");
+  if (rows * std::max(n, k) >= (int64_t)1 << 31) return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_linear: rows * max(n, k) beyond 32-bit GEMM indices");
+  return swin_linear(precision, epilogue, x_dev, w_dev, bias_dev, resid_dev, out_dev, rows, n, k, S(stream));
 }

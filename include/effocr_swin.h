@@ -80,6 +80,38 @@ int effocr_swin_forward(effocr_swin_t* enc, const float* x_dev, int batch, float
  * workspace since the last check produced a non-finite embedding, else 0. */
 int effocr_swin_check_status(const effocr_swin_t* enc, const void* workspace_dev, void* stream);
 
+/* ---- test entry points (tests/test_gpu_swin_ops.py) ------------------------------------------------------
+ * One kernel launch each, on caller-made device tensors in the kernels' own layouts, so that the tests can
+ * run every kernel and linear of the forward at shapes the 224 x 224 forward never reaches.  NULL pointers
+ * and non-positive sizes give EFFOCR_SWIN_EINVAL, a geometry the launcher does not implement
+ * EFFOCR_SWIN_EUNSUPPORTED, both before anything is launched.  LayerNorm eps is the forward's (1e-5).
+ * `precision` is the operand type of the linears as in effocr_swin_create; activations with
+ * `padded_channels` > `channels` hold pad channels that are never read on input and written as 0 on output. */
+/* x [batch,3,img_size,img_size] fp32; w [48 taps (c, ky, kx)][128], b / lnw / lnb [128] fp32 (zero beyond
+ * `channels`) -> out [batch * (img_size/4)^2][128] fp32: 4x4/s4 conv + bias + LayerNorm over `channels` */
+int effocr_swin_op_stem(const float* x_dev, int batch, int img_size, const float* w_dev, const float* b_dev,
+                        const float* lnw_dev, const float* lnb_dev, int channels, float* out_dev, void* stream);
+/* x [rows][padded_channels] fp32 -> out [rows][padded_channels] in precision's type */
+int effocr_swin_op_layernorm(int precision, const float* x_dev, int64_t rows, int channels, int padded_channels,
+                             const float* lnw_dev, const float* lnb_dev, void* out_dev, void* stream);
+/* patch merging: x [batch][map_size][map_size][padded_channels] fp32, lnw / lnb [4 channels] ->
+ * out [batch * (map_size/2)^2][4 channels] in precision's type (2x2 gather in timm's order + LayerNorm) */
+int effocr_swin_op_merge(int precision, const float* x_dev, int batch, int map_size, int channels, int padded_channels,
+                         const float* lnw_dev, const float* lnb_dev, void* out_dev, void* stream);
+/* qkv [batch * map_size^2][3][padded_channels] and out [batch * map_size^2][padded_channels] in precision's
+ * type; table [169][channels / 32] fp32; shift: the cyclic shift of SW-MSA (0 = W-MSA) */
+int effocr_swin_op_window_attention(int precision, const void* qkv_dev, int batch, int map_size, int channels,
+                                    int padded_channels, int shift, const float* table_dev, void* out_dev, void* stream);
+/* x [batch][tokens][padded_channels] fp32 -> emb [batch][channels] fp32 (LayerNorm, mean over the tokens,
+ * F.normalize when l2_normalize != 0); a non-finite embedding ORs 1 into status_dev[0] */
+int effocr_swin_op_head(const float* x_dev, int batch, int tokens, int channels, int padded_channels, const float* lnw_dev,
+                        const float* lnb_dev, int l2_normalize, float* emb_dev, int* status_dev, void* stream);
+/* out [rows][n] = epilogue(x [rows][k] . w [n][k]^T + bias [n]) through the forward's own dispatch; x and w in
+ * precision's type, bias fp32.  epilogue: 0 bias, 1 bias + GELU (both: out in precision's type), 2 bias +
+ * fp32 residual resid [rows][n] -> fp32 out (resid_dev may equal out_dev), 5 bias -> fp32 out. */
+int effocr_swin_op_linear(int precision, int epilogue, const void* x_dev, const void* w_dev, const float* bias_dev,
+                          const float* resid_dev, void* out_dev, int64_t rows, int n, int k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

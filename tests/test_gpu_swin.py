@@ -1,6 +1,10 @@
 """swin_tiny_patch4_window7_224 on the MI355X (-m gpu): parity with the CPU restatement (tests/swin_ref.py, pinned to transformers by
 tests/test_swin_host.py) in every precision, on crops whose structure sits at window borders, batch / chunk invariance, status word,
-normalisation, workspace, and the three engines end to end."""
+normalisation, workspace, and the three engines end to end.
+
+These are whole 224 x 224 forwards compared on one pooled vector per crop.  Operator parity — each kernel of csrc/swin.hip and each
+linear of the forward on its own, at small and odd shapes, against float64 within derived bounds — lives in tests/test_gpu_swin_ops.py
+(references in tests/swin_ops_ref.py, their CPU judgement in tests/test_swin_ops_host.py)."""
 
 import numpy as np
 import pytest

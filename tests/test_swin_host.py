@@ -206,7 +206,7 @@ def test_other_seeded_streams_unchanged(key):
 def test_swin_library_exports_its_header_and_versions_agree():
     src = open(os.path.join(ROOT, "include", "effocr_swin.h")).read()
     declared = sorted(set(re.findall(r"\b(effocr_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", src, flags=re.S))))
-    assert len(declared) == 15
+    assert len(declared) == 21
     raw = ctypes.CDLL(_lib.SWIN_SO_PATH)
     for n in declared:
         assert hasattr(raw, n), f"{n} declared in effocr_swin.h but not exported"
@@ -275,3 +275,52 @@ def test_swin_handle_and_refusals():
     assert L.effocr_swin_create(ARCH.encode(), 224, 1, None) == -1
     assert L.effocr_swin_forward(None, None, 1, None, 0, None, 0, None) == -1
     assert L.effocr_swin_embed_dim(None) == 0 and L.effocr_swin_num_params(None) == 0
+
+
+def test_swin_op_entry_points_check_their_arguments():
+    """Every effocr_swin_op_* call below is refused on the host, before any launch: NULL pointers, non-positive sizes, unknown precision
+    or epilogue -> -1; what the launcher cannot do -> -2; each with a message."""
+    L = _lib.swin_lib()
+    p, s = ctypes.c_void_p(4096), None                                            # (never dereferenced)
+
+    def refused(rc, code):
+        assert rc == code, (rc, L.effocr_swin_last_error())
+        assert L.effocr_swin_last_error()
+
+    stem = lambda x=p, B=1, S=8, w=p, b=p, g=p, be=p, C0=96, o=p: L.effocr_swin_op_stem(x, B, S, w, b, g, be, C0, o, s)
+    for kw in (dict(x=None), dict(w=None), dict(b=None), dict(g=None), dict(be=None), dict(o=None), dict(B=0), dict(S=0), dict(C0=0), dict(S=-4)):
+        refused(stem(**kw), -1)
+    for kw in (dict(S=10), dict(C0=132), dict(C0=94)):                            # S % 4; beyond the 128 channels; C0 % 4
+        refused(stem(**kw), -2)
+
+    ln = lambda pr=2, x=p, M=4, C=96, Cp=128, g=p, b=p, o=p: L.effocr_swin_op_layernorm(pr, x, M, C, Cp, g, b, o, s)
+    for kw in (dict(x=None), dict(g=None), dict(b=None), dict(o=None), dict(M=0), dict(C=0), dict(Cp=-128), dict(pr=3), dict(pr=-1)):
+        refused(ln(**kw), -1)
+    for kw in (dict(Cp=192, C=96), dict(Cp=1152, C=1152), dict(C=256, Cp=128), dict(C=94)):   # Cp % 128; > 1024; C > Cp; C % 4
+        refused(ln(**kw), -2)
+
+    mg = lambda pr=2, x=p, B=1, H=4, C=96, Cp=128, g=p, b=p, o=p: L.effocr_swin_op_merge(pr, x, B, H, C, Cp, g, b, o, s)
+    for kw in (dict(x=None), dict(g=None), dict(b=None), dict(o=None), dict(B=0), dict(H=0), dict(C=0), dict(Cp=0), dict(pr=3)):
+        refused(mg(**kw), -1)
+    for kw in (dict(C=48), dict(H=5), dict(C=416, Cp=512), dict(C=256, Cp=128), dict(Cp=130)):   # C % 32; odd H; C > 384; C > Cp; Cp % 4
+        refused(mg(**kw), -2)
+
+    wa = lambda pr=2, q=p, B=1, H=14, C=96, Cp=128, sh=3, t=p, o=p: L.effocr_swin_op_window_attention(pr, q, B, H, C, Cp, sh, t, o, s)
+    for kw in (dict(q=None), dict(t=None), dict(o=None), dict(B=0), dict(H=0), dict(C=0), dict(Cp=0), dict(pr=3)):
+        refused(wa(**kw), -1)
+    for kw in (dict(H=12), dict(C=48), dict(sh=7), dict(sh=-1), dict(H=7, sh=3), dict(C=256, Cp=128), dict(Cp=132)):
+        refused(wa(**kw), -2)                                                     # H % 7; C % 32; shift >= 7; < 0; with one window; ...
+
+    hd = lambda x=p, B=1, T=4, C=128, Cp=256, g=p, b=p, l2=1, e=p, st=p: L.effocr_swin_op_head(x, B, T, C, Cp, g, b, l2, e, st, s)
+    for kw in (dict(x=None), dict(g=None), dict(b=None), dict(e=None), dict(st=None), dict(B=0), dict(T=0), dict(C=0), dict(Cp=0)):
+        refused(hd(**kw), -1)
+    for kw in (dict(C=96, Cp=128), dict(C=1152, Cp=1152), dict(C=256, Cp=128), dict(Cp=258)):
+        refused(hd(**kw), -2)
+
+    li = lambda pr=2, epi=0, x=p, w=p, b=p, r=None, o=p, M=4, N=128, K=128: L.effocr_swin_op_linear(pr, epi, x, w, b, r, o, M, N, K, s)
+    for kw in (dict(x=None), dict(w=None), dict(b=None), dict(o=None), dict(M=0), dict(N=0), dict(K=0), dict(pr=3), dict(epi=3), dict(epi=4),
+               dict(epi=6), dict(epi=-1), dict(epi=2)):                            # (EPI_BIAS_RESID without a residual)
+        refused(li(**kw), -1)
+    for kw in (dict(N=192), dict(K=48), dict(pr=0, K=96), dict(M=1 << 24, N=128, K=128), dict(M=1 << 20, K=3072, N=128)):
+        refused(li(**kw), -2)
+    assert b"32-bit" in L.effocr_swin_last_error()
