@@ -362,12 +362,37 @@ def beit_lib():
     return _load_family(BEIT_SO_PATH, "beit", BEIT_ABI_VERSION, _beit_signatures(), "BEiT encoder")
 
 
+# libeffocr_bit.so (include/effocr_bit.h): the BiT ResNetV2 encoders resnetv2_50x1_bitm / resnetv2_101x1_bitm (GroupNorm + ReLU, stem pool
+# and head kernels of its own; it carries its own copies of the ResNet paths' convolutions, hidden).
+BIT_SO_PATH = os.path.join(_HERE, "libeffocr_bit.so")
+BIT_ABI_VERSION = 1     # == EFFOCR_BIT_ABI_VERSION of include/effocr_bit.h
+
+
+def _bit_signatures():
+    c = ctypes
+    vp, i32, sz = c.c_void_p, c.c_int, c.c_size_t
+    sig = _encoder_signatures("bit")
+    sig["effocr_bit_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_bit_op_groupnorm_relu"] = (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp])   # test entry points
+    sig["effocr_bit_op_stem_pool"] = (i32, [i32, vp, i32, i32, i32, i32, vp, vp])
+    sig["effocr_bit_op_head"] = (i32, [i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp])
+    return sig
+
+
+BIT_EXPORTS = tuple(sorted(_bit_signatures()))
+
+
+def bit_lib():
+    return _load_family(BIT_SO_PATH, "bit", BIT_ABI_VERSION, _bit_signatures(), "BiT ResNetV2 encoder")
+
+
 head_check = _family_check("head")
 swin_check = _family_check("swin")
 resnet_check = _family_check("resnet")
 mnv3_check = _family_check("mnv3")
 effnet_check = _family_check("effnet")
 beit_check = _family_check("beit")
+bit_check = _family_check("bit")
 
 
 def check(rc, what="", handle=None):

@@ -142,7 +142,10 @@ def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECI
         def head(self):
             if self._head is None:
                 wk, bk = W.head_keys(self.model_name)
-                self._head = HipClassifierHead(self._sd[wk], self._sd[bk], device=self._device)
+                w = self._sd[wk]
+                if w.dim() == 4:                         # BiT's head is a 1x1 convolution: [N, D, 1, 1] is the matrix [N, D]
+                    w = w.reshape(w.shape[0], w.shape[1])
+                self._head = HipClassifierHead(w, self._sd[bk], device=self._device)
             return self._head
 
         def embed(self, x):

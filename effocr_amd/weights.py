@@ -41,6 +41,13 @@ against a timm install.  The two names are the same module (they differ in their
 and ``infer_arch`` answers ``beit_base_patch16_224``.  The buffers ``attn.relative_position_index`` and ``attn.k_bias`` of older timm
 checkpoints are dropped by ``strip_prefix``.  The architecture and the shapes are pinned against ``transformers.BeitModel``
 (tests/test_beit_host.py).
+
+BiT ResNetV2 (``resnetv2_50x1_bitm`` / ``resnetv2_101x1_bitm``; timm >= 0.9 calls the same modules ``resnetv2_50x1_bit`` / ``resnetv2_101x1_bit``)
+key names follow timm's ``resnetv2.py`` as remembered (``stem.conv``, ``stages.i.blocks.j.{downsample.conv,norm1,conv1,norm2,conv2,norm3,
+conv3}``, ``norm``, classifier ``head.fc`` — a 1x1 convolution, weight [N, 2048, 1, 1]) and are UNVERIFIED against a timm install.  Every
+convolution is weight-standardised and has no bias, every norm is GroupNorm(32) + ReLU.  The ``_bitm`` and ``_bit`` names share keys and
+shapes, so ``infer_arch`` answers the ``_bitm`` name.  The architecture and the parameter counts are pinned against
+``transformers.BitModel`` (tests/test_bit_host.py).
 """
 from collections import OrderedDict
 import math
@@ -120,6 +127,16 @@ BEIT_CFG = {
     "beitv2_base_patch16_224": (768, 12, 12, 4),
     "beit_tiny_test": (128, 2, 2, 4),         # miniature used only by fast tests
 }
+BIT_CFG = {
+    # name: depths — timm resnetv2.py, PreActBottleneck, width factor 1: mid widths 64-128-256-512 (x4 out), GroupNorm(32, eps 1e-5) + ReLU
+    # before each weight-standardised conv, a final norm; the _bit names are timm >= 0.9's for the same modules
+    "resnetv2_50x1_bitm": (3, 4, 6, 3),
+    "resnetv2_50x1_bit": (3, 4, 6, 3),
+    "resnetv2_101x1_bitm": (3, 4, 23, 3),
+    "resnetv2_101x1_bit": (3, 4, 23, 3),
+}
+BIT_WIDTHS = (64, 128, 256, 512)      # bottleneck widths per stage
+BIT_FEATURES = 2048
 MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
 MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
 PATCH = 16
@@ -235,6 +252,8 @@ def embed_dim(arch):
         return EFFICIENTNET_FEATURES
     if arch in BEIT_CFG:
         return BEIT_CFG[arch][0]
+    if arch in BIT_CFG:
+        return BIT_FEATURES
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -245,6 +264,11 @@ def is_swin(arch):
 def is_beit(arch):
     """beit_base_patch16_224 / beitv2_base_patch16_224 (and the miniature beit_tiny_test): the encoders that run on libeffocr_beit.so."""
     return arch in BEIT_CFG
+
+
+def is_bit(arch):
+    """resnetv2_50x1_bitm / resnetv2_101x1_bitm (and their timm >= 0.9 names): the encoders that run on libeffocr_bit.so."""
+    return arch in BIT_CFG
 
 
 def beit_relative_position_index(W):
@@ -283,10 +307,11 @@ def is_convnext(arch):
 # efficientnet_b0 / tf_efficientnet_b0: the global average pool of SiLU(bn2(conv_head)).
 # swin_tiny_patch4_window7_224: the mean of the final norm's tokens (timm >= 0.9 names the head head.fc; strip_prefix renames timm < 0.9's head).
 # beit_base_patch16_224 / beitv2_base_patch16_224: fc_norm of the mean of the patch tokens.
+# resnetv2_*_bitm: the global average pool of relu(norm(x)); the head is a 1x1 convolution, its weight [N, 2048, 1, 1] (head_shapes).
 HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bias"),
              "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias"),
              "swin": ("head.fc.weight", "head.fc.bias"), "efficientnet": ("classifier.weight", "classifier.bias"),
-             "beit": ("head.weight", "head.bias")}
+             "beit": ("head.weight", "head.bias"), "bit": ("head.fc.weight", "head.fc.bias")}
 
 
 def _family(arch):
@@ -304,6 +329,8 @@ def _family(arch):
         return "efficientnet"
     if arch in BEIT_CFG:
         return "beit"
+    if arch in BIT_CFG:
+        return "bit"
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -313,13 +340,14 @@ def head_keys(arch):
 
 
 def head_shapes(arch, num_classes):
-    """Ordered {timm key: shape} of the classifier head: weight [num_classes, embed_dim], bias [num_classes] (empty for 0)."""
+    """Ordered {timm key: shape} of the classifier head: weight [num_classes, embed_dim] ([num_classes, embed_dim, 1, 1] for BiT, whose
+    head is a 1x1 convolution), bias [num_classes] (empty for 0)."""
     s = OrderedDict()
     if num_classes:
         if num_classes < 0:
             raise ValueError(f"num_classes must be >= 0, got {num_classes}")
         wk, bk = head_keys(arch)
-        s[wk] = (int(num_classes), embed_dim(arch))
+        s[wk] = (int(num_classes), embed_dim(arch)) + ((1, 1) if arch in BIT_CFG else ())
         s[bk] = (int(num_classes),)
     return s
 
@@ -426,7 +454,35 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _efficientnet_shapes(arch)
     if arch in BEIT_CFG:
         return _beit_shapes(arch, img_size)
+    if arch in BIT_CFG:
+        return _bit_shapes(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _bit_shapes(arch):
+    """timm's state-dict order: the shortcut convolution is the first child of a stage's first block.  No convolution has a bias and no
+    norm has running statistics (GroupNorm)."""
+    s = OrderedDict()
+    s["stem.conv.weight"] = (64, 3, 7, 7)
+    cin = 64
+    for i, (nb, mid) in enumerate(zip(BIT_CFG[arch], BIT_WIDTHS)):
+        for j in range(nb):
+            p = f"stages.{i}.blocks.{j}."
+            if j == 0:
+                s[p + "downsample.conv.weight"] = (4 * mid, cin, 1, 1)
+            s[p + "norm1.weight"] = (cin,)
+            s[p + "norm1.bias"] = (cin,)
+            s[p + "conv1.weight"] = (mid, cin, 1, 1)
+            s[p + "norm2.weight"] = (mid,)
+            s[p + "norm2.bias"] = (mid,)
+            s[p + "conv2.weight"] = (mid, mid, 3, 3)
+            s[p + "norm3.weight"] = (mid,)
+            s[p + "norm3.bias"] = (mid,)
+            s[p + "conv3.weight"] = (4 * mid, mid, 1, 1)
+            cin = 4 * mid
+    s["norm.weight"] = (cin,)
+    s["norm.bias"] = (cin,)
+    return s
 
 
 def _beit_shapes(arch, img_size):
@@ -625,6 +681,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_resnet(arch, seed, img_size, scale)
     if arch in BEIT_CFG:
         return _init_beit(arch, seed, img_size, scale)
+    if arch in BIT_CFG:
+        return _init_bit(arch, seed, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -813,6 +871,29 @@ def _init_beit(arch, seed, img_size, scale):
     return sd
 
 
+def _init_bit(arch, seed, scale):
+    """BiT ResNetV2 from a CPU Philox generator of its own.  Convolutions are N(0, 1 / fan_in) in both scales (weight standardisation
+    removes their mean and scale anyway; timm draws N(0, sqrt(2 / fan_out))).  scale="timm": GroupNorms at identity, with norm3's gamma 0
+    (timm's zero_init_last).  scale="unit": gammas U(0.5, 1.5) and betas N(0, 0.2), norm3's gamma and beta x 0.25 — so that a residual
+    branch adds a fraction of the stream, as a trained network's does, instead of doubling its variance per block."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x62697432) % (1 << 63))
+    sd = OrderedDict()
+    for k, shp in _bit_shapes(arch).items():
+        leaf = k.rsplit(".", 1)[-1]
+        last = ".norm3." in k
+        if len(shp) == 4:
+            v = torch.randn(shp, generator=g, dtype=torch.float32) / math.sqrt(shp[1] * shp[2] * shp[3])
+        elif scale == "timm":
+            v = torch.zeros(shp) if (leaf == "bias" or last) else torch.ones(shp)
+        elif leaf == "weight":
+            v = (torch.rand(shp, generator=g, dtype=torch.float32) + 0.5) * (0.25 if last else 1.0)
+        else:
+            v = torch.randn(shp, generator=g, dtype=torch.float32) * 0.2 * (0.25 if last else 1.0)
+        sd[k] = v.contiguous()
+    return sd
+
+
 def _init_resnet(arch, seed, img_size, scale):
     """resnet34 / resnet50 from a CPU Philox generator of their own (resnet18 keeps the generic stream of init_state_dict).
     Convolutions are kaiming-normal (std sqrt(2 / fan_in)), as timm's.  scale="timm": BN at identity, with the last BN of every residual
@@ -868,7 +949,7 @@ def infer_num_classes(sd):
     """Classes of the timm classifier head a checkpoint carries (rows of its head weight), 0 when it has none."""
     sd = strip_prefix(sd)
     for wk, bk in HEAD_KEYS.values():
-        if wk in sd and bk in sd and sd[wk].dim() == 2:
+        if wk in sd and bk in sd and (sd[wk].dim() == 2 or (sd[wk].dim() == 4 and tuple(sd[wk].shape[2:]) == (1, 1))):
             return int(sd[wk].shape[0])
     return 0
 
@@ -956,6 +1037,16 @@ def infer_arch(sd):
                 return name
         raise ValueError(f"unsupported ResNet: {block} blocks, depths {depths} (supported: "
                          + ", ".join(f"{n} {c[2]} {c[0]}" for n, c in RESNET_CFG.items()) + ")")
+    if "stem.conv.weight" in sd and "stages.3.blocks.0.conv3.weight" in sd and "stages.0.blocks.0.norm1.weight" in sd:
+        # BiT ResNetV2 (pre-activation bottlenecks; ConvNeXt's stem is stem.0): the depths tell 50 from 101, the shapes pin the width
+        depths = tuple(1 + max((int(k.split(".")[3]) for k in sd if k.startswith(f"stages.{i}.blocks.")), default=-1) for i in range(4))
+        for name, dep in BIT_CFG.items():
+            want = _bit_shapes(name)
+            if dep == depths and all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
+                return name
+        width = int(sd["stages.0.blocks.0.conv3.weight"].shape[0]) // 256
+        raise ValueError(f"unsupported BiT ResNetV2: depths {depths}, width factor {width} (supported: resnetv2_50x1_bitm (3, 4, 6, 3) and "
+                         "resnetv2_101x1_bitm (3, 4, 23, 3), width factor 1)")
     if "pos_embed" in sd:
         D = sd["pos_embed"].shape[-1]
         depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
@@ -1015,6 +1106,8 @@ def check_state_dict(arch, sd, img_size=224, num_classes=0):
     for k, shp in want.items():
         if k not in sd:
             bad.append(f"missing {k}")
+        elif arch in BIT_CFG and k == "head.fc.weight" and tuple(sd[k].shape) == tuple(shp[:2]):
+            continue                                   # the 1x1-conv head as a matrix [N, 2048] is accepted too
         elif tuple(sd[k].shape) != tuple(shp):
             bad.append(f"{k}: shape {tuple(sd[k].shape)} != {tuple(shp)}")
     if bad:
