@@ -386,6 +386,29 @@ def bit_lib():
     return _load_family(BIT_SO_PATH, "bit", BIT_ABI_VERSION, _bit_signatures(), "BiT ResNetV2 encoder")
 
 
+# libeffocr_vit8.so (include/effocr_vit8.h): the patch-8 ViT encoders vit_small_patch8_224 / vit_base_patch8_224 (attention that streams
+# its key tiles, an 8x8 patch im2col; it carries its own copies of the GEMMs and of the ViT helper kernels, hidden).
+VIT8_SO_PATH = os.path.join(_HERE, "libeffocr_vit8.so")
+VIT8_ABI_VERSION = 1     # == EFFOCR_VIT8_ABI_VERSION of include/effocr_vit8.h
+
+
+def _vit8_signatures():
+    c = ctypes
+    vp, i32 = c.c_void_p, c.c_int
+    sig = _encoder_signatures("vit8")
+    sig["effocr_vit8_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_vit8_op_attn"] = (i32, [vp, i32, i32, i32, i32, vp, vp])                        # test entry points
+    sig["effocr_vit8_op_patch_embed"] = (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp])
+    return sig
+
+
+VIT8_EXPORTS = tuple(sorted(_vit8_signatures()))
+
+
+def vit8_lib():
+    return _load_family(VIT8_SO_PATH, "vit8", VIT8_ABI_VERSION, _vit8_signatures(), "patch-8 ViT encoder")
+
+
 head_check = _family_check("head")
 swin_check = _family_check("swin")
 resnet_check = _family_check("resnet")
@@ -393,6 +416,7 @@ mnv3_check = _family_check("mnv3")
 effnet_check = _family_check("effnet")
 beit_check = _family_check("beit")
 bit_check = _family_check("bit")
+vit8_check = _family_check("vit8")
 
 
 def check(rc, what="", handle=None):

@@ -48,6 +48,13 @@ conv3}``, ``norm``, classifier ``head.fc`` — a 1x1 convolution, weight [N, 204
 convolution is weight-standardised and has no bias, every norm is GroupNorm(32) + ReLU.  The ``_bitm`` and ``_bit`` names share keys and
 shapes, so ``infer_arch`` answers the ``_bitm`` name.  The architecture and the parameter counts are pinned against
 ``transformers.BitModel`` (tests/test_bit_host.py).
+
+Patch-8 ViTs (``vit_small_patch8_224`` / ``vit_base_patch8_224``) use the key names of timm's ``vision_transformer.py`` that the patch-16
+ViTs above already use (``cls_token``, ``pos_embed``, ``patch_embed.proj``, ``blocks.i.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}``,
+``norm``, classifier ``head``); only ``patch_embed.proj.weight`` is [D, 3, 8, 8] and ``pos_embed`` has (img_size / 8)^2 + 1 rows.  They
+could not be checked against a timm install either; the architecture and the parameter counts are pinned against
+``transformers.ViTModel(patch_size=8)`` (tests/test_vit8_host.py).  ``infer_arch`` tells patch 8 from patch 16 by the kernel size of
+``patch_embed.proj.weight``.
 """
 from collections import OrderedDict
 import math
@@ -137,6 +144,14 @@ BIT_CFG = {
 }
 BIT_WIDTHS = (64, 128, 256, 512)      # bottleneck widths per stage
 BIT_FEATURES = 2048
+VIT8_CFG = {
+    # name: (embed_dim, depth, heads, mlp_ratio) — timm vision_transformer.py with patch_size 8 (vit_small_patch8_224 carries the DINO
+    # ViT-S/8 weights); the same pre-norm blocks as VIT_CFG's, 785 tokens per 224^2 crop; they run on libeffocr_vit8.so
+    "vit_small_patch8_224": (384, 12, 6, 4),
+    "vit_base_patch8_224": (768, 12, 12, 4),
+    "vit8_tiny_test": (128, 2, 2, 4),         # miniature used only by fast tests
+}
+VIT8_PATCH = 8
 MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
 MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
 PATCH = 16
@@ -254,6 +269,8 @@ def embed_dim(arch):
         return BEIT_CFG[arch][0]
     if arch in BIT_CFG:
         return BIT_FEATURES
+    if arch in VIT8_CFG:
+        return VIT8_CFG[arch][0]
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -269,6 +286,12 @@ def is_beit(arch):
 def is_bit(arch):
     """resnetv2_50x1_bitm / resnetv2_101x1_bitm (and their timm >= 0.9 names): the encoders that run on libeffocr_bit.so."""
     return arch in BIT_CFG
+
+
+def is_vit8(arch):
+    """vit_small_patch8_224 / vit_base_patch8_224 (and the miniature vit8_tiny_test): the encoders that run on libeffocr_vit8.so.
+    ``is_vit`` stays False for them: nothing routes them to the product library."""
+    return arch in VIT8_CFG
 
 
 def beit_relative_position_index(W):
@@ -307,11 +330,13 @@ def is_convnext(arch):
 # efficientnet_b0 / tf_efficientnet_b0: the global average pool of SiLU(bn2(conv_head)).
 # swin_tiny_patch4_window7_224: the mean of the final norm's tokens (timm >= 0.9 names the head head.fc; strip_prefix renames timm < 0.9's head).
 # beit_base_patch16_224 / beitv2_base_patch16_224: fc_norm of the mean of the patch tokens.
+# vit_small_patch8_224 / vit_base_patch8_224: norm(x)[:, 0], as the patch-16 ViTs.
 # resnetv2_*_bitm: the global average pool of relu(norm(x)); the head is a 1x1 convolution, its weight [N, 2048, 1, 1] (head_shapes).
 HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bias"),
              "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias"),
              "swin": ("head.fc.weight", "head.fc.bias"), "efficientnet": ("classifier.weight", "classifier.bias"),
-             "beit": ("head.weight", "head.bias"), "bit": ("head.fc.weight", "head.fc.bias")}
+             "beit": ("head.weight", "head.bias"), "bit": ("head.fc.weight", "head.fc.bias"),
+             "vit8": ("head.weight", "head.bias")}
 
 
 def _family(arch):
@@ -331,6 +356,8 @@ def _family(arch):
         return "beit"
     if arch in BIT_CFG:
         return "bit"
+    if arch in VIT8_CFG:
+        return "vit8"
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -456,7 +483,39 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _beit_shapes(arch, img_size)
     if arch in BIT_CFG:
         return _bit_shapes(arch)
+    if arch in VIT8_CFG:
+        return _vit8_shapes(arch, img_size)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _vit8_shapes(arch, img_size):
+    """timm's state-dict order for a VisionTransformer with patch_size 8: the patch-16 table with an 8x8 patch conv and
+    (img_size / 8)^2 + 1 position rows."""
+    D, depth, heads, r = VIT8_CFG[arch]
+    if img_size % VIT8_PATCH or not VIT8_PATCH <= img_size <= 224:
+        raise ValueError(f"{arch}: img_size must be a multiple of {VIT8_PATCH} from {VIT8_PATCH} to 224, got {img_size}")
+    s = OrderedDict()
+    s["cls_token"] = (1, 1, D)
+    s["pos_embed"] = (1, (img_size // VIT8_PATCH) ** 2 + 1, D)
+    s["patch_embed.proj.weight"] = (D, 3, VIT8_PATCH, VIT8_PATCH)
+    s["patch_embed.proj.bias"] = (D,)
+    for i in range(depth):
+        p = f"blocks.{i}."
+        s[p + "norm1.weight"] = (D,)
+        s[p + "norm1.bias"] = (D,)
+        s[p + "attn.qkv.weight"] = (3 * D, D)
+        s[p + "attn.qkv.bias"] = (3 * D,)
+        s[p + "attn.proj.weight"] = (D, D)
+        s[p + "attn.proj.bias"] = (D,)
+        s[p + "norm2.weight"] = (D,)
+        s[p + "norm2.bias"] = (D,)
+        s[p + "mlp.fc1.weight"] = (r * D, D)
+        s[p + "mlp.fc1.bias"] = (r * D,)
+        s[p + "mlp.fc2.weight"] = (D, r * D)
+        s[p + "mlp.fc2.bias"] = (D,)
+    s["norm.weight"] = (D,)
+    s["norm.bias"] = (D,)
+    return s
 
 
 def _bit_shapes(arch):
@@ -683,6 +742,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_beit(arch, seed, img_size, scale)
     if arch in BIT_CFG:
         return _init_bit(arch, seed, scale)
+    if arch in VIT8_CFG:
+        return _init_vit8(arch, seed, img_size, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -871,6 +932,43 @@ def _init_beit(arch, seed, img_size, scale):
     return sd
 
 
+def _init_vit8(arch, seed, img_size, scale):
+    """Patch-8 ViT seeded init from a CPU Philox generator of its own.  scale="timm": trunc_normal(0.02) linears, patch conv and
+    pos_embed, cls token N(0, 1e-6), LayerNorms at identity, zero biases — what timm's initialiser gives.  scale="unit": fan-in-scaled
+    linears and patch conv, cls token and pos_embed N(0, 0.5), LayerNorm gains U(0.5, 1.5), biases N(0, 0.1): attention over the 785
+    tokens is far from uniform and no term of the forward is switched off.  scale="trained": the unit rule with the magnitudes of a
+    trained ViT — pos_embed and cls token N(0, 0.1), attn.proj and mlp.fc2 at a quarter of the fan-in scale, so that a block adds a
+    fraction of the residual stream instead of doubling its variance."""
+    if scale not in ("unit", "timm", "trained"):
+        raise ValueError(f"scale must be 'unit', 'timm' or 'trained', got {scale!r}")
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x76697438) % (1 << 63))
+    sd = OrderedDict()
+
+    def randn(shape, std):
+        return torch.randn(shape, generator=g, dtype=torch.float32) * std
+
+    for k, shp in _vit8_shapes(arch, img_size).items():
+        leaf = k.rsplit(".", 1)[-1]
+        is_ln = "norm" in k
+        if scale == "timm":
+            if k == "cls_token":
+                v = randn(shp, 1e-6)
+            elif len(shp) == 1:
+                v = torch.ones(shp) if (leaf == "weight" and is_ln) else torch.zeros(shp)
+            else:
+                v = randn(shp, 0.02).clamp_(-0.04, 0.04)
+        elif k in ("cls_token", "pos_embed"):
+            v = randn(shp, 0.5 if scale == "unit" else 0.1)
+        elif len(shp) == 1:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5 if (leaf == "weight" and is_ln) else randn(shp, 0.1)
+        else:
+            gain = 0.25 if (scale == "trained" and (".attn.proj." in k or ".mlp.fc2." in k)) else 1.0
+            v = randn(shp, gain / math.sqrt(math.prod(shp[1:])))
+        sd[k] = v.contiguous()
+    return sd
+
+
 def _init_bit(arch, seed, scale):
     """BiT ResNetV2 from a CPU Philox generator of its own.  Convolutions are N(0, 1 / fan_in) in both scales (weight standardisation
     removes their mean and scale anyway; timm draws N(0, sqrt(2 / fan_out))).  scale="timm": GroupNorms at identity, with norm3's gamma 0
@@ -1025,6 +1123,15 @@ def beit_img_size(sd):
     return (w2 + 1) // 2 * PATCH
 
 
+def vit8_img_size(sd):
+    """Crop size a patch-8 ViT checkpoint was built for, from the (img_size / 8)^2 + 1 rows of its ``pos_embed``."""
+    n = int(strip_prefix(sd)["pos_embed"].shape[-2])
+    w = math.isqrt(max(n - 1, 0))
+    if n < 2 or w * w != n - 1 or w > 224 // VIT8_PATCH:
+        raise ValueError(f"unsupported patch-8 ViT: a pos_embed of {n} rows is not W^2 + 1 for a patch grid W <= 28")
+    return w * VIT8_PATCH
+
+
 def infer_arch(sd):
     """Guess the architecture of a checkpoint from its parameter shapes."""
     sd = strip_prefix(sd)
@@ -1050,6 +1157,13 @@ def infer_arch(sd):
     if "pos_embed" in sd:
         D = sd["pos_embed"].shape[-1]
         depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        pw = sd.get("patch_embed.proj.weight")
+        if pw is not None and pw.dim() == 4 and int(pw.shape[-1]) == VIT8_PATCH:
+            # the same keys as the patch-16 ViTs: the kernel size of the patch conv tells them apart
+            for name, (d, dep, _, _) in VIT8_CFG.items():
+                if d == D and dep == depth:
+                    return name
+            raise ValueError(f"unsupported patch-8 ViT: width {D}, depth {depth} (supported: small, width 384, and base, width 768, depth 12)")
         for name, (d, dep, _, _) in VIT_CFG.items():
             if d == D and dep == depth:
                 return name
