@@ -60,7 +60,10 @@ struct effocr_encoder {
   int debug = 0;
   int cls_only_last = 1;            // last block: attn.proj + MLP only on the class-token rows (the only rows that reach the output); 0: all tokens (A/B switch)
   int mlp_stagger_min_rounds = 2;   // ... from this many rounds of CUs on (512-crop calls: +7.7 %, 384: +3.5 %, same box; no effect below two rounds)
-  int mlp_stagger = 3500;           // fused MLP: start spread of the first round of workgroups, clock ticks per step of 32 (0 = off)
+  int mlp_tail_first = 96;          // fused MLP: this many split parts of the tail run FIRST, on the last phases of that spread, instead of last (mlp_roles.hpp; 0 = off).
+                                    // Same box, two interleaved rounds, with mlp_stagger 3500 -> 2500 (EXPERIMENTS 7-2): 1024 crops -1.1 %, 576 crops -3.4 %, 896 -1.6 %, fp16 -1.0 %
+  int mlp_stagger = 2500;           // fused MLP: start spread of the first round of workgroups, clock ticks per step of 32 (0 = off); the 20 phases that still wait
+                                    // cover [0, 50 k ticks), the others are offset by the part they run first (~60 k ticks at 1024 crops)
   int use_projf = 1;                // 1: attn.proj + residual fused in front of the fused MLP kernel (the new row stays in the accumulators: -0.9 ms and -0.6 GB of HBM traffic per forward vs the separate row-panel launch); 0: A/B switch
   int use_qkvattn = 1;              // fused norm1 + attn.qkv + attention kernel (qkvattn.hip): no qkv tensor in HBM (0: A/B switch)
   int qa_min_batch = 1;             // fused qkv+attention from this many crops per call on (below: the token-panel LN+qkv kernel + attention kernel)
@@ -710,7 +713,7 @@ int vit_forward(effocr_encoder* e, const void* x, int x16, int B, float* emb, in
         MlpArgs m{};
         m.x = xs; m.gamma = F(L.ln2w); m.beta = F(L.ln2b); m.eps = 1e-6f; m.W1b = wb + L.fc1w_b; m.b1 = F(L.fc1b);
         m.W2p = wb + L.fc2w_pp; m.b2 = F(L.fc2b_p); m.b2_logical = F(L.fc2b); m.M = M; m.D = D; m.H = e->vit.mlp; m.rows_alloc = (int)w.rows;
-        m.partial = reinterpret_cast<float*>(hb); m.partial_bytes = w.hbytes; m.no_tail_split = !e->tail_split; m.no_split6 = !e->split6; m.pair = e->mlp_pair; m.no_pair_parts = !e->pair_parts; m.stagger = e->mlp_stagger; m.stagger_min_rounds = e->mlp_stagger_min_rounds;   // the hidden buffer is free on this path
+        m.partial = reinterpret_cast<float*>(hb); m.partial_bytes = w.hbytes; m.no_tail_split = !e->tail_split; m.no_split6 = !e->split6; m.pair = e->mlp_pair; m.no_pair_parts = !e->pair_parts; m.stagger = e->mlp_stagger; m.stagger_min_rounds = e->mlp_stagger_min_rounds; m.tail_first = e->mlp_tail_first;   // the hidden buffer is free on this path
         if (e->call_size_invariant) { m.no_tail_split = 1; m.pair = -1; }   // whole panels only: no hidden split (a reordered fc2 sum), no pair form
         if (projf) {                                     // attn.proj + residual runs inside the same kernel, in front
           m.A = att; m.Wpp = wb + L.projw_pp; m.bp = F(L.projb_p);
@@ -1163,6 +1166,7 @@ int effocr_encoder_set_option(effocr_encoder_t* enc, const char* name, int value
   if (n == "use_projf") { enc->use_projf = value; return EFFOCR_OK; }
   if (n == "cls_only_last") { enc->cls_only_last = value; return EFFOCR_OK; }
   if (n == "mlp_stagger_min_rounds") { enc->mlp_stagger_min_rounds = value < 1 ? 1 : value; return EFFOCR_OK; }
+  if (n == "mlp_tail_first") { enc->mlp_tail_first = value < 0 ? 0 : value & ~7; return EFFOCR_OK; }
   if (n == "mlp_stagger") { enc->mlp_stagger = value < 0 ? 0 : value; return EFFOCR_OK; }
   if (n == "panel_rows") { if (value != 64 && value != 128) return fail(EFFOCR_EINVAL, "set_option: panel_rows must be 64 or 128"); enc->panel_rows = value; return EFFOCR_OK; }
   if (n == "call_size_invariant") {

@@ -41,6 +41,7 @@
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mlp_roles.hpp"
 #include <type_traits>
 
 #ifndef MLP_BARRIER_DRAIN
@@ -68,6 +69,9 @@
 #ifndef MLP_PRE_STAGES
 #define MLP_PRE_STAGES 3                                 // ring stages requested in front of the prologue's wait (the rest behind its barrier)
 #endif
+#ifndef MLP_TAIL_FIRST_JITTER
+#define MLP_TAIL_FIRST_JITTER 0                          // start wait of the workgroups that run a split part first (tail_first): 0 = none, n = spread over n phases of mlp_stagger ticks
+#endif
 #ifndef MLP_NT
 #define MLP_NT 15                                        // non-temporal: 1 row loads, 2 attention-fragment loads, 4 row stores, 8 second-output stores
 #endif
@@ -88,8 +92,13 @@ __device__ unsigned long long mlp_stamps[MLP_STAMP_WGS * MLP_STAMP_N];
 #ifndef MLP_STAMP_PART
 #define MLP_STAMP_PART false                             // true: the split parts stamp instead of the whole panels (small calls)
 #endif
+#ifndef MLP_STAMP_ALL
+#define MLP_STAMP_ALL false                              // true: EVERY workgroup of a launch stamps, whole panels and split parts, in the row of its block id; slot 19 =
+#endif                                                   // its role, (index << 1) | part (tools/mlp_timeline.py --gantt: the launch-level schedule)
+#define MLP_STAMP_ON (MLP_STAMP_ALL || PARTIAL == MLP_STAMP_PART)
+#define MLP_STAMP_ROW (((MLP_STAMP_ALL ? (int)blockIdx.x : bid) & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N)
 #define MLP_STAMP_AT(k)                                                                                          \
-  if constexpr (PARTIAL == MLP_STAMP_PART) mlp_stamps[(bid & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N + (k)] = __builtin_amdgcn_s_memtime();
+  if constexpr (MLP_STAMP_ON) mlp_stamps[MLP_STAMP_ROW + (k)] = __builtin_amdgcn_s_memtime();
 #else
 #define MLP_STAMP_AT(k)
 #endif
@@ -216,15 +225,24 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a, const int bid) 
   };
   MLP_STAMP_AT(0)
 #ifdef MLP_STAMP
-  if (PARTIAL == MLP_STAMP_PART) mlp_stamps[(bid & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N + 14] = __builtin_amdgcn_s_memrealtime();
-  if (PARTIAL == MLP_STAMP_PART) mlp_stamps[(bid & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N + 15] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
+  if (MLP_STAMP_ON) mlp_stamps[MLP_STAMP_ROW + 14] = __builtin_amdgcn_s_memrealtime();
+  if (MLP_STAMP_ALL) mlp_stamps[MLP_STAMP_ROW + 19] = ((unsigned long long)bid << 1) | (PARTIAL ? 1 : 0);
+  if (MLP_STAMP_ON) mlp_stamps[MLP_STAMP_ROW + 15] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
 #endif
   // First round of workgroups only: spread the start over `stagger` x 32 ticks.  All panels cost the same, so the
   // workgroups of a launch otherwise stay in lock step from the first to the last round: every CU requests its rows at the
   // same moment (61 MB per round: an HBM-bound 12 us during which nothing computes) and stores them at the same moment.
-  if (!PARTIAL && a.stagger > 0 && bid < a.stagger_wgs) {
+  // tail_first > 0 (mlp_roles.hpp): the last tail_first / 8 phases of the round run a split part first instead — their offset is the
+  // part's time, not a sleep — and only the phases in front of them wait (mlp_stagger is then sized so that they cover a part's time).
+  if (!PARTIAL && a.stagger > 0 && bid < a.stagger_wgs - a.tail_first) {
     const unsigned long long until = __builtin_amdgcn_s_memtime() + (unsigned long long)(((bid >> 3) & 31) * a.stagger);
     while (__builtin_amdgcn_s_memtime() < until) __builtin_amdgcn_s_sleep(8);
+  }
+  if constexpr (PARTIAL && !PAIR && MLP_TAIL_FIRST_JITTER > 0) {   // the part-first workgroups (parts [0, tail_first)): a few phases of jitter
+    if (a.stagger > 0 && bid < a.tail_first) {
+      const unsigned long long until = __builtin_amdgcn_s_memtime() + (unsigned long long)(((bid >> 3) % MLP_TAIL_FIRST_JITTER) * a.stagger);
+      while (__builtin_amdgcn_s_memtime() < until) __builtin_amdgcn_s_sleep(8);
+    }
   }
   MLP_STAMP_AT(1)
   constexpr int SPLIT = (H / 128) / NCW;                 // workgroups per panel
@@ -1192,25 +1210,27 @@ __device__ __forceinline__ void mlp_fused_body(const MlpArgs& a, const int bid) 
   }
   MLP_STAMP_AT(10)
 #ifdef MLP_STAMP
-  if constexpr (PARTIAL == MLP_STAMP_PART) { mlp_stamps[(bid & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N + 12] = vm_wait; mlp_stamps[(bid & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N + 13] = bar_wait; }
+  if constexpr (MLP_STAMP_ON) { mlp_stamps[MLP_STAMP_ROW + 12] = vm_wait; mlp_stamps[MLP_STAMP_ROW + 13] = bar_wait; }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
   MLP_STAMP_AT(11)
 #ifdef MLP_STAMP
-  if (PARTIAL == MLP_STAMP_PART) mlp_stamps[(bid & (MLP_STAMP_WGS - 1)) * MLP_STAMP_N + 16] = __builtin_amdgcn_s_memrealtime();
+  if (MLP_STAMP_ON) mlp_stamps[MLP_STAMP_ROW + 16] = __builtin_amdgcn_s_memrealtime();
 #endif
 }
 
-// One launch for the whole panels (workgroups [0, main_wgs)) AND the split parts of the tail panels (TNCW hidden chunks each; TNCW = 0:
-// no tail): the parts are dispatched last, i.e. into the ragged end that the start spread of the first round leaves on the CUs.
+// One launch for the whole panels AND the split parts of the tail panels (TNCW hidden chunks each; TNCW = 0: no tail).  mlp_role
+// (mlp_roles.hpp) says which one a block id runs: the whole panels first and the parts last, i.e. into the ragged end that the start
+// spread of the first round leaves on the CUs — or, tail_first > 0, the first tail_first parts in the last phases of the first round.
 template <typename E, int D, int H, int TNCW, bool PROJ>
 __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(MlpArgs a) {
   if constexpr (TNCW == 0) {
     mlp_fused_body<E, D, H, H / 128, false, PROJ>(a, (int)blockIdx.x);
   } else {
-    if ((int)blockIdx.x < a.main_wgs) mlp_fused_body<E, D, H, H / 128, false, PROJ>(a, (int)blockIdx.x);
+    const MlpRole role = mlp_role_clamped((int)blockIdx.x, a.main_wgs, a.stagger_wgs, a.tail_first);   // (the launcher clamped tail_first)
+    if (!role.part) mlp_fused_body<E, D, H, H / 128, false, PROJ>(a, role.index);
     else {
-      const int b = (int)blockIdx.x - a.main_wgs;
+      const int b = role.index;
       if constexpr (PROJ) {                              // part 0 of a panel keeps the new row, the others start at zero (KEEP)
         if (b % ((H / 128) / TNCW) == 0) mlp_fused_body<E, D, H, TNCW, true, true, false, true>(a, b);
         else mlp_fused_body<E, D, H, TNCW, true, true, false, false>(a, b);
@@ -1281,6 +1301,8 @@ int launch_mlp(const MlpArgs& a_in, hipStream_t s) {
   for (const void* q : {(const void*)a.b1, (const void*)a.b2, (const void*)a.gamma, (const void*)a.beta, (const void*)a.bp, (const void*)a.gamma_n, (const void*)a.beta_n})
     if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(EFFOCR_EINVAL, "mlp_fused: bias / LayerNorm parameter arrays must be 16-byte aligned (they reach LDS by 16-byte DMA)");
   const int npanels = (a.M + MLP_PT - 1) / MLP_PT;
+  const int tail_first_opt = a.tail_first;               // honoured below where a launch has a start spread and a split tail, 0 for every other form
+  a.tail_first = 0;
   if (a.D == 128 && a.H == 512) {
     a.panel0 = 0; a.main_wgs = npanels; a.stagger_wgs = 0;
     hipLaunchKernelGGL((mlp_fused_kernel<E, 128, 512, 0, PROJ>), dim3((unsigned)npanels), dim3(256), 0, s, a);
@@ -1332,7 +1354,8 @@ int launch_mlp(const MlpArgs& a_in, hipStream_t s) {
   a.panel0 = main_panels;                                // first split panel
   a.main_wgs = main_panels;
   a.tail_rb = tail * 4;
-  a.stagger_wgs = main_panels >= (a.stagger_min_rounds > 0 ? a.stagger_min_rounds : 4) * slots ? slots : 0;  // (the spread costs ~0.4 panel times at the end of the launch; measured worth it from 2 rounds on: api.hip)
+  a.stagger_wgs = main_panels >= (a.stagger_min_rounds > 0 ? a.stagger_min_rounds : 4) * slots ? slots : 0;  // (measured per workgroup, 1024 crops, every part last: the spread costs 0.31 panel times of sleep per CU and leaves 0.32 idle at the end of the launch — tools/mlp_timeline.py --gantt, KERNELS "launch-level schedule"; worth it from 2 rounds on: api.hip)
+  a.tail_first = a.stagger > 0 ? mlp_tail_first_clamp(tail_first_opt, main_panels, tail, split, a.stagger_wgs) : 0;   // (mlp_roles.hpp: what mlp_role_clamped at the kernel's entry relies on)
   const dim3 grid((unsigned)(main_panels + (split > 1 ? tail * split : 0)));
   if (split == 6) hipLaunchKernelGGL((mlp_fused_kernel<E, 384, 1536, 2, PROJ>), grid, dim3(256), 0, s, a);
   else if (split == 4) hipLaunchKernelGGL((mlp_fused_kernel<E, 384, 1536, 3, PROJ>), grid, dim3(256), 0, s, a);

@@ -142,8 +142,11 @@ int effocr_encoder_set_chunk(effocr_encoder_t* enc, int crops_per_chunk);
  *                 64-token pair panels over 6 / 3 / 2 workgroups + the reduction launch (0: 128-token panels over six / four, whole pair panels from 30 crops)
  *   "mlp_pair"    [0] fused proj+MLP: 64-token panels whose wave pairs split a chunk's hidden features (no partial sums in HBM, no
  *                 reduction launch): 0 = for calls of 37..83 crops (below: "pair_parts"), 1 = whenever the 64-token panels fit one round of CUs, -1 = never
- *   "mlp_stagger" [3500] fused MLP kernel: the first round of workgroups starts spread over 32 x this many clock ticks, so
+ *   "mlp_stagger" [2500] fused MLP kernel: the first round of workgroups starts spread over 32 x this many clock ticks, so
  *                 that the CUs do not request / store their rows all at the same moment (0 = off)
+ *   "mlp_tail_first" [96] fused MLP kernel: where a launch has that spread and a tail of panels cut into parts, this many parts (a multiple
+ *                 of 8, at most all of them) run first, on the workgroups of the last start phases, instead of at the end of the launch: those
+ *                 CUs are offset by a part's work, not by a sleep.  Bit-identical results (0 = every part last)
  *   "mlp_stagger_min_rounds" [2] ... for launches of at least this many rounds of CUs (512-crop calls: +7.7 %; no effect below two)
  *   "use_projf"   [1] attn.proj + residual fused in front of the fused MLP kernel (0: its own row-panel launch)
  *   "use_patchf"  [1] fused im2col + patch-embedding GEMM (embed dims 128 / 256 / 384 / 768); 0: im2col kernel + DMA-ring GEMM

@@ -10,6 +10,7 @@ objs=""
 for o in *.o; do
   src=${o%.o}.hip
   case $o in panel.o|mlp_bf16.o|mlp_f16.o) continue;; esac   # A/B-only objects (make AB=1): the variant is a PRODUCT library (ab_stubs.o stands in)
+  case $o in *.*.o|head.o) continue;; esac                   # objects of the other libraries (libeffocr_swin.so ... libeffocr_convops.so, libeffocr_head.so)
   if [[ " $* " == *" $src "* ]]; then
     flags=""; [ "$src" = qkvattn.hip ] && flags="-mllvm -amdgpu-mfma-vgpr-form"
     [[ "$src" == mlp*.hip ]] && flags="-fno-slp-vectorize"
