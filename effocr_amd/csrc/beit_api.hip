@@ -3,7 +3,7 @@
 // compiles a second time with hidden visibility) and the library's own error state.  All device memory is caller-owned; this file
 // allocates host memory only.
 #include "../../include/effocr_beit.h"
-#include "enc_core.hpp"
+#include "token_core.hpp"
 #include "beit.hpp"
 
 #include <memory>
@@ -19,7 +19,7 @@ constexpr int BEIT_PATCH = 16, BEIT_PATCH_K = 3 * BEIT_PATCH * BEIT_PATCH;
 constexpr size_t BEIT_WS_BUDGET = (size_t)1000 << 20;
 constexpr int BEIT_MAX_CHUNK = 256;
 
-struct BlockOff { size_t ln1w, ln1b, qkvw, qkvb, table, projw, projb, g1, ln2w, ln2b, fc1w, fc1b, fc2w, fc2b, g2; };
+struct BlockOff : TokenBlockOff { size_t table; };
 
 }  // namespace
 }  // namespace effocr
@@ -61,13 +61,9 @@ void build_beit(effocr_beit* e) {
     e->add_param(q + "mlp.fc1.weight", (int64_t)4 * D * D); e->add_param(q + "mlp.fc1.bias", 4 * D);
     e->add_param(q + "mlp.fc2.weight", (int64_t)4 * D * D); e->add_param(q + "mlp.fc2.bias", D);
     BlockOff& L = e->blk[i];
-    L.ln1w = a.take((size_t)D * 4); L.ln1b = a.take((size_t)D * 4);
-    L.qkvw = a.take((size_t)3 * D * D * es); L.qkvb = a.take((size_t)3 * D * 4);
-    L.table = a.take((size_t)entries * heads * 4);
-    L.projw = a.take((size_t)D * D * es); L.projb = a.take((size_t)D * 4); L.g1 = a.take((size_t)D * 4);
-    L.ln2w = a.take((size_t)D * 4); L.ln2b = a.take((size_t)D * 4);
-    L.fc1w = a.take((size_t)4 * D * D * es); L.fc1b = a.take((size_t)4 * D * 4);
-    L.fc2w = a.take((size_t)4 * D * D * es); L.fc2b = a.take((size_t)D * 4); L.g2 = a.take((size_t)D * 4);
+    take_norm1_qkv(a, L, D, es); L.table = a.take((size_t)entries * heads * 4);
+    take_proj(a, L, D, es); L.g1 = a.take((size_t)D * 4);
+    take_mlp(a, L, D, es); L.g2 = a.take((size_t)D * 4);
   }
   e->add_param("fc_norm.weight", D); e->add_param("fc_norm.bias", D);
   e->fcnw = a.take((size_t)D * 4); e->fcnb = a.take((size_t)D * 4);
@@ -77,80 +73,48 @@ void build_beit(effocr_beit* e) {
 // Packing: fp32 vectors and bias tables as they are; linear weights [N][K] rounded once to the operand type; the qkv bias vector is
 // [q_bias | 0 | v_bias] (the key projection has no bias); the position rows of the patch-embedding epilogue stay zero.
 void pack_beit(const effocr_beit* e, std::vector<char>& blob) {
-  auto f32 = [&](size_t off, const std::string& n) { const auto& v = e->P(n); put_f32(blob, off, v.data(), v.size()); };
-  auto op = [&](size_t off, const std::string& n) { const auto& v = e->P(n); put_op(blob, off, v.data(), v.size(), e->prec); };
-  const int D = e->D;
-  f32(e->cls, "cls_token");
-  op(e->patchw, "patch_embed.proj.weight"); f32(e->patchb, "patch_embed.proj.bias");
+  const Packer p{e, blob};
+  p.f32(e->cls, "cls_token");
+  p.op(e->patchw, "patch_embed.proj.weight"); p.f32(e->patchb, "patch_embed.proj.bias");
   for (int i = 0; i < e->depth; ++i) {
     const std::string q = "blocks." + std::to_string(i) + ".";
     const BlockOff& L = e->blk[i];
-    f32(L.ln1w, q + "norm1.weight"); f32(L.ln1b, q + "norm1.bias");
-    f32(L.ln2w, q + "norm2.weight"); f32(L.ln2b, q + "norm2.bias");
-    f32(L.g1, q + "gamma_1"); f32(L.g2, q + "gamma_2");
-    f32(L.table, q + "attn.relative_position_bias_table");
-    f32(L.qkvb, q + "attn.q_bias"); f32(L.qkvb + (size_t)2 * D * 4, q + "attn.v_bias");
-    op(L.qkvw, q + "attn.qkv.weight");
-    op(L.projw, q + "attn.proj.weight"); f32(L.projb, q + "attn.proj.bias");
-    op(L.fc1w, q + "mlp.fc1.weight"); f32(L.fc1b, q + "mlp.fc1.bias");
-    op(L.fc2w, q + "mlp.fc2.weight"); f32(L.fc2b, q + "mlp.fc2.bias");
+    pack_token_block(p, L, q);
+    p.f32(L.g1, q + "gamma_1"); p.f32(L.g2, q + "gamma_2");
+    p.f32(L.table, q + "attn.relative_position_bias_table");
+    p.f32(L.qkvb, q + "attn.q_bias"); p.f32(L.qkvb + (size_t)2 * e->D * 4, q + "attn.v_bias");
   }
-  f32(e->fcnw, "fc_norm.weight"); f32(e->fcnb, "fc_norm.bias");
+  p.f32(e->fcnw, "fc_norm.weight"); p.f32(e->fcnb, "fc_norm.bias");
 }
 
-// workspace of one sub-batch of B crops: status word, fp32 residual [B T][D], the operand buffer A (patch rows [B P][768], LayerNorm
-// and attention outputs [B T][D]) and the buffer Q of the qkv output [B T][3D] / the hidden [B T][4D] (never live at once).
-struct BeitWs { size_t status, x, a, q, total; };
-BeitWs beit_ws(const effocr_beit* e, int B) {
-  const size_t es = prec_esize(e->prec), M = (size_t)B * e->T, D = e->D;
-  Alloc a; BeitWs w;
-  w.status = a.take(256);                   // int32 status word at workspace offset 0 (effocr_beit_check_status)
-  w.x = a.take(M * D * 4);
-  w.a = a.take(std::max(M * D, (size_t)B * (e->T - 1) * BEIT_PATCH_K) * es);
-  w.q = a.take(M * 4 * D * es);
-  w.total = a.off;
-  return w;
-}
+// workspace of one sub-batch of B crops: token_core.hpp's layout with patch rows [B P][768]
+TokenWs beit_ws(const effocr_beit* e, int B) { return token_ws(B, e->T, e->D, BEIT_PATCH_K, prec_esize(e->prec)); }
 
 int beit_chunk(const effocr_beit* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) c = (int)std::min<size_t>(BEIT_MAX_CHUNK, std::max<size_t>(1, BEIT_WS_BUDGET / beit_ws(e, 1).total));
-  return c < batch ? c : batch;
+  return enc_default_chunk(e, batch, BEIT_WS_BUDGET, BEIT_MAX_CHUNK, [e](int B) { return beit_ws(e, B).total; });
 }
 
 // One sub-batch: im2col -> patch GEMM into rows 1.. of every crop, cls row -> blocks (LN1 -> qkv -> bias attention -> proj, layer scale
 // + residual; LN2 -> fc1 + GELU -> fc2, layer scale + residual) -> head.  Every GEMM's kernel is chosen by (precision, N, K) alone and
 // reduces K in a fixed order (no split-K); the attention kernel by the token count: a crop's embedding does not depend on B.
 int beit_forward(const effocr_beit* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
-  const BeitWs w = beit_ws(e, B);
+  const TokenWs w = beit_ws(e, B);
   const char* wb = e->wdev;
   const int prec = e->prec, D = e->D, T = e->T, P = T - 1;
-  const int64_t M = (int64_t)B * T;
   auto F = [&](size_t off) { return reinterpret_cast<const float*>(wb + off); };
   float* xs = reinterpret_cast<float*>(ws + w.x);
   void* A = ws + w.a; void* Q = ws + w.q;
   int* status = reinterpret_cast<int*>(ws + w.status);
   int rc;
-  auto lin = [&](const void* X, int K, size_t woff, size_t boff, void* out, int N, int epi, int64_t rows, size_t scale) {
-    GemmArgs g{};
-    g.X = X; g.ldx = K; g.W = wb + woff; g.ldw = K; g.bias = F(boff); g.out = out; g.ldo = N; g.M = (int)rows; g.N = N; g.K = K;
-    if (epi == EPI_BIAS_SCALE_RESID) { g.resid = xs; g.ldr = N; g.scale = F(scale); }
-    if (epi == EPI_PATCH) { g.pos = F(e->pos0); g.P = P; }
-    return gemm2_supported(prec, N, K) ? gemm2_nt(prec, epi, g, s) : gemm_nt(prec, epi, g, s);
-  };
+  LinearExtras patch{};
+  patch.pos = F(e->pos0); patch.P = P;
   if ((rc = im2col_patch16(prec, x, 0, B, e->img, e->img, A, s))) return rc;
-  if ((rc = lin(A, BEIT_PATCH_K, e->patchw, e->patchb, xs, D, EPI_PATCH, (int64_t)B * P, 0))) return rc;
+  if ((rc = dense_linear(prec, EPI_PATCH, A, BEIT_PATCH_K, wb + e->patchw, F(e->patchb), xs, D, (int64_t)B * P, patch, s))) return rc;
   if ((rc = set_cls_rows(F(e->cls), xs, B, T, D, 0, nullptr, s))) return rc;
-  for (int i = 0; i < e->depth; ++i) {
-    const BlockOff& L = e->blk[i];
-    if ((rc = layernorm_rows(prec, xs, M, D, F(L.ln1w), F(L.ln1b), BEIT_EPS, A, s))) return rc;
-    if ((rc = lin(A, D, L.qkvw, L.qkvb, Q, 3 * D, EPI_BIAS, M, 0))) return rc;
-    if ((rc = beit_attention(prec, Q, F(L.table), B, e->W, e->heads, A, s))) return rc;
-    if ((rc = lin(A, D, L.projw, L.projb, xs, D, EPI_BIAS_SCALE_RESID, M, L.g1))) return rc;
-    if ((rc = layernorm_rows(prec, xs, M, D, F(L.ln2w), F(L.ln2b), BEIT_EPS, A, s))) return rc;
-    if ((rc = lin(A, D, L.fc1w, L.fc1b, Q, 4 * D, EPI_BIAS_GELU, M, 0))) return rc;
-    if ((rc = lin(Q, 4 * D, L.fc2w, L.fc2b, xs, D, EPI_BIAS_SCALE_RESID, M, L.g2))) return rc;
-  }
+  const TokenRun run{prec, wb, (int64_t)B * T, D, BEIT_EPS, xs, A, Q, s};
+  if ((rc = token_blocks(run, e->blk, EPI_BIAS_SCALE_RESID, [&](const BlockOff& L, const void* qkv, void* out) {
+         return beit_attention(prec, qkv, F(L.table), B, e->W, e->heads, out, s);
+       }))) return rc;
   return beit_head(xs, B, T, D, F(e->fcnw), F(e->fcnb), BEIT_EPS, l2, emb, status, s);
 }
 
@@ -206,7 +170,7 @@ BEIT_API int effocr_beit_forward(effocr_beit_t* enc, const float* x_dev, int bat
   const int rc = enc_forward_args("beit", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_beit_workspace_bytes(enc, batch));
   if (rc || batch == 0) return rc;
   const int chunk = beit_chunk(enc, batch);
-  if ((int64_t)chunk * enc->T * 4 * enc->D >= (int64_t)1 << 31)
+  if (!token_index_ok(chunk, enc->T, enc->D))
     return fail(EFFOCR_BEIT_EUNSUPPORTED, "beit_forward: chunk too large for 32-bit GEMM indices (effocr_beit_set_chunk)");
   return enc_forward_chunks(enc, x_dev, batch, chunk, emb_dev, [&](const float* x, int crops, float* emb) {
     return beit_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
@@ -214,16 +178,11 @@ BEIT_API int effocr_beit_forward(effocr_beit_t* enc, const float* x_dev, int bat
 }
 
 BEIT_API int effocr_beit_check_status(const effocr_beit_t* enc, const void* workspace_dev, void* stream) {   // BeitWs::status = offset 0
-  return enc_check_status("beit", enc, workspace_dev, stream,
-                          "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
-                          "input was not finite; use precision bf16 or fp32 for this checkpoint");
+  return enc_check_status("beit", enc, workspace_dev, stream, ENC_F16_OPERAND_OVERFLOW);
 }
 
 BEIT_API int effocr_beit_reset_status(const effocr_beit_t* enc, void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_BEIT_EINVAL, "beit_reset_status: NULL argument");
-  const hipError_t er = hipMemsetAsync(workspace_dev, 0, sizeof(int), S(stream));
-  if (er != hipSuccess) return fail(EFFOCR_BEIT_EHIP, std::string("beit_reset_status: ") + hipGetErrorString(er));
-  return EFFOCR_BEIT_OK;
+  return enc_reset_status("beit", enc, workspace_dev, stream);
 }
 
 BEIT_API int effocr_beit_op_attn(const void* qkv_dev, const float* table_dev, int batch, int patches_per_side, int heads, int dtype,

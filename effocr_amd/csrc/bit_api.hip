@@ -4,8 +4,7 @@
 // modes, resnet.hip's exact-fp32 pipeline with its split-K turned off in the fp32 mode — both with an all-zero bias vector, no ReLU, and
 // the residual on conv3.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_bit.h"
-#include "enc_core.hpp"
-#include "resnet16.hpp"
+#include "resnet_core.hpp"
 #include "bit.hpp"
 
 #include <math.h>
@@ -19,11 +18,10 @@ namespace {
 // sub-batches: as many crops as keep the workspace under BIT_WS_BUDGET (1 GB < 1 GiB), at most BIT_MAX_CHUNK
 constexpr size_t BIT_WS_BUDGET = (size_t)1000 << 20;
 constexpr int BIT_MAX_CHUNK = 256;
-constexpr int BIT_STEM_K32 = 160;   // fp32 stem im2col columns (resnet.hip's im2col_conv1: 147 taps padded to 5 K-stages of 32)
 constexpr int BIT_WIDTH = 2048;     // the widest layer: length of the shared zero bias
 
-// one weight-standardised convolution: timm key, geometry and blob offset (weights [cout][kpad] in the operand type)
-struct Conv { std::string w; int cin, cout, k, stride, pad, kpad; size_t w_off; };
+// one weight-standardised convolution: geometry and timm key
+struct Conv : ConvGeom { std::string w; };
 // one GroupNorm: timm key prefix, channels and blob offsets (gamma, beta [C] fp32)
 struct Norm { std::string p; int C; size_t g_off, b_off; };
 // one pre-activation bottleneck: convs[c0 ..] = (downsample,) conv1, conv2, conv3; norms[n0 ..] = norm1, norm2, norm3
@@ -47,7 +45,7 @@ namespace {
 
 void add_conv(effocr_bit* e, const std::string& w, int cin, int cout, int k, int stride, int pad) {
   e->add_param(w, (int64_t)cout * cin * k * k);
-  e->convs.push_back(Conv{w, cin, cout, k, stride, pad, k * k * cin, 0});
+  e->convs.push_back(Conv{{cin, cout, k, stride, pad, k * k * cin, 0}, w});
 }
 void add_norm(effocr_bit* e, const std::string& p, int C, int HW) {
   e->add_param(p + ".weight", C); e->add_param(p + ".bias", C);
@@ -60,7 +58,7 @@ void add_norm(effocr_bit* e, const std::string& p, int C, int HW) {
 void build_bit(effocr_bit* e, int depth2) {
   const int depths[4] = {3, 4, depth2, 3}, widths[4] = {64, 128, 256, 512};
   add_conv(e, "stem.conv.weight", 3, 64, 7, 2, 3);
-  e->convs[0].kpad = e->prec == PREC_FP32 ? BIT_STEM_K32 : RN_STEM_K16;
+  e->convs[0].kpad = e->prec == PREC_FP32 ? RES_STEM_K32 : RN_STEM_K16;
   int cin = 64, H = e->img / 4;
   for (int si = 0; si < 4; ++si) {
     const int mid = widths[si], cout = 4 * mid;
@@ -96,21 +94,16 @@ void pack_bit(const effocr_bit* e, std::vector<char>& blob) {
   for (const Conv& c : e->convs) {
     const auto& w = e->P(c.w);
     const size_t fan = (size_t)c.cin * c.k * c.k;
-    std::vector<float> wd((size_t)c.cout * c.kpad, 0.f);
+    std::vector<double> mean(c.cout), sc(c.cout);
     for (int co = 0; co < c.cout; ++co) {
       const float* wc = w.data() + (size_t)co * fan;
-      double mean = 0.0, var = 0.0;
-      for (size_t i = 0; i < fan; ++i) mean += (double)wc[i];
-      mean /= (double)fan;
-      for (size_t i = 0; i < fan; ++i) { const double d = (double)wc[i] - mean; var += d * d; }
-      const double sc = 1.0 / sqrt(var / (double)fan + 1e-8);
-      for (int ky = 0; ky < c.k; ++ky)
-        for (int kx = 0; kx < c.k; ++kx)
-          for (int cc = 0; cc < c.cin; ++cc) {
-            const float v = wc[((size_t)cc * c.k + ky) * c.k + kx];
-            wd[(size_t)co * c.kpad + (ky * c.k + kx) * c.cin + cc] = (float)(((double)v - mean) * sc);
-          }
+      double m = 0.0, var = 0.0;
+      for (size_t i = 0; i < fan; ++i) m += (double)wc[i];
+      m /= (double)fan;
+      for (size_t i = 0; i < fan; ++i) { const double d = (double)wc[i] - m; var += d * d; }
+      mean[co] = m; sc[co] = 1.0 / sqrt(var / (double)fan + 1e-8);
     }
+    const std::vector<float> wd = relayout_ohwi(w, c, mean, sc);
     put_op(blob, c.w_off, wd.data(), wd.size(), e->prec);
   }
   for (const Norm& n : e->norms) {
@@ -119,49 +112,20 @@ void pack_bit(const effocr_bit* e, std::vector<char>& blob) {
   }
 }
 
-// Workspace of one sub-batch of B crops: the status word, the GroupNorm tile statistics and four activation buffers, each as large as the
-// largest activation (the stem's output, S/2 x S/2 x 64, equals stage 0's output S/4 x S/4 x 256).  The stem's im2col rows overlay
-// buffers 1-3, which are free until the pool.
-struct BitWs { size_t status, gn, buf[4], total; };
-BitWs bit_ws(const effocr_bit* e, int B) {
-  const size_t es = prec_esize(e->prec);
-  const size_t s2 = (size_t)(e->img / 2) * (e->img / 2);
-  const size_t act = align_up((size_t)B * s2 * 64 * es, 256);
-  const size_t col = (size_t)B * s2 * e->convs[0].kpad * es;
-  Alloc a; BitWs w;
-  w.status = a.take(256);                   // int32 status word at workspace offset 0 (effocr_bit_check_status)
-  w.gn = a.take((size_t)B * e->gn_tiles * BIT_GROUPS * BIT_GN_REC * sizeof(float));
-  w.buf[0] = a.take(act);
-  const size_t rest = a.take(std::max(3 * act, col));
-  for (int i = 1; i < 4; ++i) w.buf[i] = rest + (size_t)(i - 1) * act;
-  w.total = a.off;
-  return w;
+// workspace of one sub-batch of B crops: resnet_core.hpp's four buffers, with the GroupNorm tile statistics as the block of its own
+ResWs bit_ws(const effocr_bit* e, int B) {
+  return res_ws(B, e->img, e->convs[0].kpad, prec_esize(e->prec), (size_t)B * e->gn_tiles * BIT_GROUPS * BIT_GN_REC * sizeof(float));
 }
 
 int bit_chunk(const effocr_bit* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) c = (int)std::min<size_t>(BIT_MAX_CHUNK, std::max<size_t>(1, BIT_WS_BUDGET / bit_ws(e, 1).total));
-  return c < batch ? c : batch;
+  return enc_default_chunk(e, batch, BIT_WS_BUDGET, BIT_MAX_CHUNK, [e](int B) { return bit_ws(e, B).total; });
 }
 
-// one weight-standardised convolution, no bias (the shared zeros), no ReLU, + residual.  16-bit modes: resnet16.hip's kernel; fp32:
-// resnet.hip's with no split-K scratch (its split count would depend on the number of output pixels, i.e. on the call size).
+const float* zero_bias(const effocr_bit* e) { return reinterpret_cast<const float*>(e->wdev + e->zero_off); }
+
+// one weight-standardised convolution, no bias (the shared zeros), no ReLU, + residual
 int conv(const effocr_bit* e, const Conv& c, const void* in, int B, int H, int W, int OH, int OW, const void* resid, void* out, hipStream_t s) {
-  const char* wb = e->wdev;
-  const float* zero = reinterpret_cast<const float*>(wb + e->zero_off);
-  if (e->prec == PREC_FP32) {
-    ConvArgs a{};
-    a.in = static_cast<const float*>(in); a.w = reinterpret_cast<const float*>(wb + c.w_off);
-    a.bias = zero; a.resid = static_cast<const float*>(resid); a.out = static_cast<float*>(out);
-    a.B = B; a.H = H; a.W = W; a.Cin = c.kpad / (c.k * c.k); a.Cout = c.cout; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
-    a.OH = OH; a.OW = OW; a.relu = 0;
-    return conv2d_nhwc(a, s);
-  }
-  Conv16Args a{};
-  a.in = in; a.w = wb + c.w_off; a.bias = zero; a.resid = resid; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = c.kpad / (c.k * c.k); a.Cout = c.cout; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
-  a.OH = OH; a.OW = OW; a.relu = 0;
-  return rn_conv16(e->prec, a, s);
+  return launch_conv(e->prec, e->wdev, c, zero_bias(e), in, B, H, W, OH, OW, resid, 0, out, s);
 }
 
 int gn(const effocr_bit* e, const Norm& n, const void* in, void* out, int B, int HW, float* partial, hipStream_t s) {
@@ -174,27 +138,20 @@ int gn(const effocr_bit* e, const Norm& n, const void* in, void* out, int B, int
 // A block with input x in buf[cur]: p = gn1(x) -> t0; shortcut = downsample(p) -> t2 (first block of a stage) or x; conv1(p) -> t1, gn2 in
 // place; conv2 -> t0, gn3 in place; conv3 + shortcut -> t1, the next block's input.
 int bit_forward(const effocr_bit* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
-  const BitWs w = bit_ws(e, B);
-  const bool f32 = e->prec == PREC_FP32;
+  const ResWs w = bit_ws(e, B);
   void* buf[4];
   for (int i = 0; i < 4; ++i) buf[i] = ws + w.buf[i];
   int* status = reinterpret_cast<int*>(ws + w.status);
-  float* part = reinterpret_cast<float*>(ws + w.gn);
+  float* part = reinterpret_cast<float*>(ws + w.extra);
   int rc;
-  int H = e->img, OH = H / 2;
-  void* col = buf[1];
-  if ((rc = f32 ? im2col_conv1(x, static_cast<float*>(col), B, H, H, OH, OH, s) : rn_im2col16(e->prec, x, col, B, H, H, OH, OH, s))) return rc;
-  // the stem's im2col rows as a 1x1 convolution over B*OH*OH "images" of one pixel
-  Conv stem = e->convs[0];
-  stem.k = 1; stem.stride = 1; stem.pad = 0;
-  if ((rc = conv(e, stem, col, B * OH * OH, 1, 1, 1, 1, nullptr, buf[0], s))) return rc;
-  H = OH; OH = (H - 1) / 2 + 1;
+  if ((rc = stem_as_1x1(e->prec, e->wdev, e->convs[0], zero_bias(e), x, buf[1], B, e->img, 0, buf[0], s))) return rc;
+  int H = e->img / 2, OH = (H - 1) / 2 + 1;
   if ((rc = bit_stem_pool(e->prec, buf[0], buf[1], B, H, H, 64, OH, OH, s))) return rc;
   H = OH;
   int cur = 1;                                          // buf[cur] holds the block input
   for (const Block& b : e->blocks) {
-    int t[3], n = 0;
-    for (int i = 0; i < 4; ++i) if (i != cur) t[n++] = i;
+    int t[3];
+    free_bufs(cur, t);
     const int Ho = (H - 1) / b.stride + 1;
     const Conv* cv = e->convs.data() + b.c0 + (b.down ? 1 : 0);
     const Norm* nm = e->norms.data() + b.n0;
@@ -265,8 +222,7 @@ BIT_API int effocr_bit_forward(effocr_bit_t* enc, const float* x_dev, int batch,
   const int rc = enc_forward_args("bit", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_bit_workspace_bytes(enc, batch));
   if (rc || batch == 0) return rc;
   const int chunk = bit_chunk(enc, batch);
-  const int64_t s2 = (int64_t)(enc->img / 2) * (enc->img / 2);
-  if ((int64_t)chunk * s2 * enc->convs[0].kpad >= (int64_t)1 << 31 || chunk > 65535)
+  if (!res_index_ok(chunk, enc->img, enc->convs[0].kpad) || chunk > 65535)
     return fail(EFFOCR_BIT_EUNSUPPORTED, "bit_forward: chunk too large for 32-bit activation indices (effocr_bit_set_chunk)");
   return enc_forward_chunks(enc, x_dev, batch, chunk, emb_dev, [&](const float* x, int crops, float* emb) {
     return bit_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
@@ -280,10 +236,7 @@ BIT_API int effocr_bit_check_status(const effocr_bit_t* enc, const void* workspa
 }
 
 BIT_API int effocr_bit_reset_status(const effocr_bit_t* enc, void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_BIT_EINVAL, "bit_reset_status: NULL argument");
-  const hipError_t er = hipMemsetAsync(workspace_dev, 0, sizeof(int), S(stream));
-  if (er != hipSuccess) return fail(EFFOCR_BIT_EHIP, std::string("bit_reset_status: ") + hipGetErrorString(er));
-  return EFFOCR_BIT_OK;
+  return enc_reset_status("bit", enc, workspace_dev, stream);
 }
 
 // ---------------------------------------------------------------- test entry points (one operator per call)

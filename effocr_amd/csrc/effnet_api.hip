@@ -151,12 +151,7 @@ EfWs effnet_ws(const effocr_effnet* e, int B) {
 }
 
 int effnet_chunk(const effocr_effnet* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) {
-    c = (int)std::min<size_t>(EF_MAX_CHUNK, std::max<size_t>(1, EF_WS_BUDGET / effnet_ws(e, 1).total));
-    while (c > 1 && effnet_ws(e, c).total > EF_WS_BUDGET) --c;     // (the per-buffer alignment is not linear in the crop count)
-  }
-  return c < batch ? c : batch;
+  return enc_default_chunk(e, batch, EF_WS_BUDGET, EF_MAX_CHUNK, [e](int B) { return effnet_ws(e, B).total; });
 }
 
 // One sub-batch: stem -> 16 blocks -> conv_head (+ bn2 + SiLU) -> global average pool -> F.normalize / status.
@@ -265,10 +260,7 @@ EFFNET_API int effocr_effnet_check_status(const effocr_effnet_t* enc, const void
 }
 
 EFFNET_API int effocr_effnet_reset_status(const effocr_effnet_t* enc, void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_EFFNET_EINVAL, "effnet_reset_status: NULL argument");
-  const hipError_t er = hipMemsetAsync(workspace_dev, 0, sizeof(int), S(stream));
-  if (er != hipSuccess) return fail(EFFOCR_EFFNET_EHIP, std::string("effnet_reset_status: ") + hipGetErrorString(er));
-  return EFFOCR_EFFNET_OK;
+  return enc_reset_status("effnet", enc, workspace_dev, stream);
 }
 
 EFFNET_API int effocr_effnet_op_stem(const float* x_dev, int batch, int img_size, int pad_before, const float* w_dev, const float* b_dev,

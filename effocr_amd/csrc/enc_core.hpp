@@ -1,6 +1,7 @@
-// Host-side core of the C-ABI libraries: the error plumbing common.hpp declares, the small packing helpers and — for the encoder-family
-// libraries (swin_api.hip, resnet_api.hip, mnv3g_api.hip, effnet_api.hip) — the handle's shared fields and the bodies of the entry
-// points that do not depend on the family.  No kernel and no device memory: everything here runs once per handle or once per call.
+// Host-side core of the C-ABI libraries: the error plumbing common.hpp declares, the small packing helpers and — for every
+// encoder-family library (each <family>_api.hip whose handle derives from EncoderCore) — the handle's shared fields, the default
+// sub-batch size and the bodies of the entry points that do not depend on the family.  token_core.hpp (Swin, BEiT, patch-8 ViT) and
+// resnet_core.hpp (ResNet-34/50, BiT) build on it.  No kernel and no device memory: everything here runs once per handle or once per call.
 //
 // Include it from exactly ONE translation unit per shared library (its *_api.hip).  The error plumbing below is that library's
 // definition of set_error / fail / check_launch / device_cus for every kernel file linked into it, and g_err is that library's own
@@ -128,6 +129,19 @@ static inline int enc_set_chunk(const char* fam, EncoderCore* e, int crops_per_c
   return EFFOCR_OK;
 }
 
+// crops per sub-batch: the handle's own setting, else as many as keep ws_total(crops) — the family's workspace size — within `budget`, at
+// most max_chunk; never more than the batch.  The shrink loop matters only where the per-buffer alignment makes ws_total grow faster than
+// the crop count (EfficientNet); where every buffer is linear in the crop count it ends at once.
+template <typename WsTotal>
+int enc_default_chunk(const EncoderCore* e, int batch, size_t budget, int max_chunk, WsTotal ws_total) {
+  int c = e->chunk;
+  if (c <= 0) {
+    c = (int)std::min<size_t>(max_chunk, std::max<size_t>(1, budget / ws_total(1)));
+    while (c > 1 && ws_total(c) > budget) --c;
+  }
+  return c < batch ? c : batch;
+}
+
 // The argument checks of effocr_<family>_forward; `need` is the family's workspace_bytes(batch) (0 for a NULL handle).  A batch of 0
 // passes them: the caller returns before it touches a pointer.
 static inline int enc_forward_args(const char* fam, const EncoderCore* e, const void* x_dev, int batch, const float* emb_dev,
@@ -153,6 +167,14 @@ int enc_forward_chunks(const EncoderCore* e, const float* x_dev, int batch, int 
   return EFFOCR_OK;
 }
 
+// What enc_check_status reports in the f16 mode, where more than one family words it alike.
+constexpr const char* ENC_F16_OPERAND_OVERFLOW =
+    "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
+    "input was not finite; use precision bf16 or fp32 for this checkpoint";
+constexpr const char* ENC_F16_ACTIVATION_OVERFLOW =
+    "forward: non-finite embedding — an f16 activation overflowed (beyond 65504) or the input was not finite; use "
+    "precision bf16 or fp32 for this checkpoint";
+
 // Read and clear the sticky status word at workspace offset 0 (synchronises `stream`).  fp16_msg: what the family's f16 mode can overflow.
 static inline int enc_check_status(const char* fam, const EncoderCore* e, const void* workspace_dev, void* stream, const char* fp16_msg) {
   if (!e || !workspace_dev) return fail(EFFOCR_EINVAL, std::string(fam) + "_check_status: NULL argument");
@@ -163,6 +185,14 @@ static inline int enc_check_status(const char* fam, const EncoderCore* e, const 
   if (er != hipSuccess) return fail(EFFOCR_EHIP, std::string(fam) + "_check_status: " + hipGetErrorString(er));
   if (st != 0)
     return fail(EFFOCR_EOVERFLOW, e->prec == PREC_FP16 ? fp16_msg : "forward: non-finite embedding — the input crops or the weights hold inf / nan");
+  return EFFOCR_OK;
+}
+
+// Clear the status word without reading it (asynchronous on `stream`).
+static inline int enc_reset_status(const char* fam, const EncoderCore* e, void* workspace_dev, void* stream) {
+  if (!e || !workspace_dev) return fail(EFFOCR_EINVAL, std::string(fam) + "_reset_status: NULL argument");
+  const hipError_t er = hipMemsetAsync(workspace_dev, 0, sizeof(int), S(stream));
+  if (er != hipSuccess) return fail(EFFOCR_EHIP, std::string(fam) + "_reset_status: " + hipGetErrorString(er));
   return EFFOCR_OK;
 }
 

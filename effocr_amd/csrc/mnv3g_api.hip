@@ -180,9 +180,7 @@ MgWs mnv3_ws(const effocr_mnv3* e, int B) {
 }
 
 int mnv3_chunk(const effocr_mnv3* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) c = (int)std::min<size_t>(MG_MAX_CHUNK, std::max<size_t>(1, MG_WS_BUDGET / mnv3_ws(e, 1).total));
-  return c < batch ? c : batch;
+  return enc_default_chunk(e, batch, MG_WS_BUDGET, MG_MAX_CHUNK, [e](int B) { return mnv3_ws(e, B).total; });
 }
 
 // One sub-batch: stem -> blocks -> ConvBnAct -> global average pool -> conv_head (+ hard-swish) -> F.normalize / status.

@@ -3,8 +3,7 @@
 // fp32 mode runs the exact-fp32 convolution pipeline of resnet.hip, which this library compiles a second time with hidden visibility, with
 // its split-K turned off.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_resnet.h"
-#include "enc_core.hpp"
-#include "resnet16.hpp"
+#include "resnet_core.hpp"
 
 #include <math.h>
 #include <memory>
@@ -17,10 +16,9 @@ namespace {
 // sub-batches: as many crops as keep the workspace under RN_WS_BUDGET (1 GB < 1 GiB), at most RN_MAX_CHUNK
 constexpr size_t RN_WS_BUDGET = (size_t)1000 << 20;
 constexpr int RN_MAX_CHUNK = 256;
-constexpr int RN_STEM_K32 = 160;   // fp32 stem im2col columns (resnet.hip's im2col_conv1: 147 taps padded to 5 K-stages of 32)
 
-// one convolution + its BatchNorm: timm key prefixes, geometry and blob offsets (weights [cout][kpad], bias [cout] fp32)
-struct Conv { std::string w, bn; int cin, cout, k, stride, pad, kpad; size_t w_off, b_off; };
+// one convolution + its BatchNorm: geometry, timm key prefixes and the blob offset of the bias [cout] fp32
+struct Conv : ConvGeom { std::string w, bn; size_t b_off; };
 // one residual block: convs[c0 ..] = conv1, conv2 (, conv3) (, downsample)
 struct Block { int c0, nconv, stride; bool down; };
 
@@ -41,7 +39,7 @@ namespace {
 void add_conv(effocr_resnet* e, const std::string& w, const std::string& bn, int cin, int cout, int k, int stride, int pad) {
   e->add_param(w, (int64_t)cout * cin * k * k);
   e->add_bn(bn, cout);
-  e->convs.push_back(Conv{w, bn, cin, cout, k, stride, pad, k * k * cin, 0, 0});
+  e->convs.push_back(Conv{{cin, cout, k, stride, pad, k * k * cin, 0}, w, bn, 0});
 }
 
 // timm resnet34 (BasicBlock) / resnet50 (Bottleneck): depths 3-4-6-3, widths 64-128-256-512 (x4 expansion for the bottleneck),
@@ -50,7 +48,7 @@ void build_resnet(effocr_resnet* e) {
   static const int depths[4] = {3, 4, 6, 3}, widths[4] = {64, 128, 256, 512};
   const int exp = e->bottleneck ? 4 : 1;
   add_conv(e, "conv1.weight", "bn1", 3, 64, 7, 2, 3);
-  e->convs[0].kpad = e->prec == PREC_FP32 ? RN_STEM_K32 : RN_STEM_K16;
+  e->convs[0].kpad = e->prec == PREC_FP32 ? RES_STEM_K32 : RN_STEM_K16;
   int cin = 64;
   for (int li = 0; li < 4; ++li) {
     const int w = widths[li], cout = w * exp;
@@ -89,89 +87,49 @@ void pack_resnet(const effocr_resnet* e, std::vector<char>& blob) {
     const auto& w = e->P(c.w);
     const auto& g = e->P(c.bn + ".weight"); const auto& bt = e->P(c.bn + ".bias");
     const auto& mu = e->P(c.bn + ".running_mean"); const auto& var = e->P(c.bn + ".running_var");
-    std::vector<float> wd((size_t)c.cout * c.kpad, 0.f);
+    std::vector<double> sc(c.cout);
     float* bd = reinterpret_cast<float*>(blob.data() + c.b_off);
     for (int co = 0; co < c.cout; ++co) {
-      const double sc = (double)g[co] / sqrt((double)var[co] + 1e-5);
-      bd[co] = (float)((double)bt[co] - (double)mu[co] * sc);
-      for (int ky = 0; ky < c.k; ++ky)
-        for (int kx = 0; kx < c.k; ++kx)
-          for (int cc = 0; cc < c.cin; ++cc) {
-            const float v = w[(((size_t)co * c.cin + cc) * c.k + ky) * c.k + kx];
-            wd[(size_t)co * c.kpad + (ky * c.k + kx) * c.cin + cc] = (float)((double)v * sc);
-          }
+      sc[co] = (double)g[co] / sqrt((double)var[co] + 1e-5);
+      bd[co] = (float)((double)bt[co] - (double)mu[co] * sc[co]);
     }
+    const std::vector<float> wd = relayout_ohwi(w, c, std::vector<double>(c.cout, 0.0), sc);   // w - 0.0 is exact
     put_op(blob, c.w_off, wd.data(), wd.size(), e->prec);
   }
 }
 
-// Workspace of one sub-batch of B crops: the status word and four activation buffers, each as large as the largest activation (the stem's
-// output, S/2 x S/2 x 64, equals resnet50's layer1 output S/4 x S/4 x 256).  The stem's im2col rows overlay buffers 1-3, which are free
-// until the max pool.
-struct RnWs { size_t status, buf[4], total; };
-RnWs resnet_ws(const effocr_resnet* e, int B) {
-  const size_t es = prec_esize(e->prec);
-  const size_t s2 = (size_t)(e->img / 2) * (e->img / 2);
-  const size_t act = align_up((size_t)B * s2 * 64 * es, 256);
-  const size_t col = (size_t)B * s2 * e->convs[0].kpad * es;
-  Alloc a; RnWs w;
-  w.status = a.take(256);                   // int32 status word at workspace offset 0 (effocr_resnet_check_status)
-  w.buf[0] = a.take(act);
-  const size_t rest = a.take(std::max(3 * act, col));
-  for (int i = 1; i < 4; ++i) w.buf[i] = rest + (size_t)(i - 1) * act;
-  w.total = a.off;
-  return w;
-}
+// workspace of one sub-batch of B crops: resnet_core.hpp's four buffers, nothing of its own
+ResWs resnet_ws(const effocr_resnet* e, int B) { return res_ws(B, e->img, e->convs[0].kpad, prec_esize(e->prec), 0); }
 
 int resnet_chunk(const effocr_resnet* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) c = (int)std::min<size_t>(RN_MAX_CHUNK, std::max<size_t>(1, RN_WS_BUDGET / resnet_ws(e, 1).total));
-  return c < batch ? c : batch;
+  return enc_default_chunk(e, batch, RN_WS_BUDGET, RN_MAX_CHUNK, [e](int B) { return resnet_ws(e, B).total; });
 }
 
-// one convolution (+ folded BN) with the epilogue: + residual, ReLU.  16-bit modes: resnet16.hip's kernel; fp32: resnet.hip's with no
-// split-K scratch (its split count would depend on the number of output pixels, i.e. on the call size).
+const float* bias_of(const effocr_resnet* e, const Conv& c) { return reinterpret_cast<const float*>(e->wdev + c.b_off); }
+
+// one convolution (+ folded BN) with the epilogue: + residual, ReLU
 int conv(const effocr_resnet* e, const Conv& c, const void* in, int B, int H, int W, int OH, int OW, const void* resid, int relu, void* out,
          hipStream_t s) {
-  const char* wb = e->wdev;
-  if (e->prec == PREC_FP32) {
-    ConvArgs a{};
-    a.in = static_cast<const float*>(in); a.w = reinterpret_cast<const float*>(wb + c.w_off);
-    a.bias = reinterpret_cast<const float*>(wb + c.b_off); a.resid = static_cast<const float*>(resid); a.out = static_cast<float*>(out);
-    a.B = B; a.H = H; a.W = W; a.Cin = c.kpad / (c.k * c.k); a.Cout = c.cout; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
-    a.OH = OH; a.OW = OW; a.relu = relu;
-    return conv2d_nhwc(a, s);
-  }
-  Conv16Args a{};
-  a.in = in; a.w = wb + c.w_off; a.bias = reinterpret_cast<const float*>(wb + c.b_off); a.resid = resid; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = c.kpad / (c.k * c.k); a.Cout = c.cout; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
-  a.OH = OH; a.OW = OW; a.relu = relu;
-  return rn_conv16(e->prec, a, s);
+  return launch_conv(e->prec, e->wdev, c, bias_of(e, c), in, B, H, W, OH, OW, resid, relu, out, s);
 }
 
 // One sub-batch: stem (im2col + 1x1 GEMM, bn1, ReLU) -> max pool -> 16 residual blocks -> global average pool (+ F.normalize).
 int resnet_forward(const effocr_resnet* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
-  const RnWs w = resnet_ws(e, B);
+  const ResWs w = resnet_ws(e, B);
   const bool f32 = e->prec == PREC_FP32;
   void* buf[4];
   for (int i = 0; i < 4; ++i) buf[i] = ws + w.buf[i];
   int* status = reinterpret_cast<int*>(ws + w.status);
   int rc;
-  int H = e->img, OH = H / 2;
-  void* col = buf[1];
-  if ((rc = f32 ? im2col_conv1(x, static_cast<float*>(col), B, H, H, OH, OH, s) : rn_im2col16(e->prec, x, col, B, H, H, OH, OH, s))) return rc;
-  // the stem's im2col rows as a 1x1 convolution over B*OH*OH "images" of one pixel
-  Conv stem = e->convs[0];
-  stem.k = 1; stem.stride = 1; stem.pad = 0;
-  if ((rc = conv(e, stem, col, B * OH * OH, 1, 1, 1, 1, nullptr, 1, buf[0], s))) return rc;
-  H = OH; OH = (H - 1) / 2 + 1;
+  if ((rc = stem_as_1x1(e->prec, e->wdev, e->convs[0], bias_of(e, e->convs[0]), x, buf[1], B, e->img, 1, buf[0], s))) return rc;
+  int H = e->img / 2, OH = (H - 1) / 2 + 1;
   if ((rc = f32 ? maxpool3x3s2_nhwc(static_cast<float*>(buf[0]), static_cast<float*>(buf[1]), B, H, H, 64, OH, OH, s)
                 : rn_maxpool16(e->prec, buf[0], buf[1], B, H, H, 64, OH, OH, s))) return rc;
   H = OH;
   int cur = 1;                                          // buf[cur] holds the block input
   for (const Block& b : e->blocks) {
-    int t[3], n = 0;
-    for (int i = 0; i < 4; ++i) if (i != cur) t[n++] = i;
+    int t[3];
+    free_bufs(cur, t);
     const int Ho = (H - 1) / b.stride + 1;
     const Conv* cv = e->convs.data() + b.c0;
     const void* idt = buf[cur];
@@ -244,8 +202,7 @@ RESNET_API int effocr_resnet_forward(effocr_resnet_t* enc, const float* x_dev, i
   const int rc = enc_forward_args("resnet", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_resnet_workspace_bytes(enc, batch));
   if (rc || batch == 0) return rc;
   const int chunk = resnet_chunk(enc, batch);
-  const int64_t s2 = (int64_t)(enc->img / 2) * (enc->img / 2);
-  if ((int64_t)chunk * s2 * enc->convs[0].kpad >= (int64_t)1 << 31)
+  if (!res_index_ok(chunk, enc->img, enc->convs[0].kpad))
     return fail(EFFOCR_RESNET_EUNSUPPORTED, "resnet_forward: chunk too large for 32-bit activation indices (effocr_resnet_set_chunk)");
   return enc_forward_chunks(enc, x_dev, batch, chunk, emb_dev, [&](const float* x, int crops, float* emb) {
     return resnet_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
@@ -253,7 +210,5 @@ RESNET_API int effocr_resnet_forward(effocr_resnet_t* enc, const float* x_dev, i
 }
 
 RESNET_API int effocr_resnet_check_status(const effocr_resnet_t* enc, const void* workspace_dev, void* stream) {   // RnWs::status = offset 0
-  return enc_check_status("resnet", enc, workspace_dev, stream,
-                          "forward: non-finite embedding — an f16 activation overflowed (beyond 65504) or the input was not finite; use "
-                          "precision bf16 or fp32 for this checkpoint");
+  return enc_check_status("resnet", enc, workspace_dev, stream, ENC_F16_ACTIVATION_OVERFLOW);
 }

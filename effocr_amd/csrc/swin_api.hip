@@ -2,7 +2,7 @@
 // orchestration over swin.hip's kernels and the GEMMs of gemm.hip / gemm2.hip, which this library compiles a second time with hidden
 // visibility) and the library's own error state.  All device memory is caller-owned; this file allocates host memory only.
 #include "../../include/effocr_swin.h"
-#include "enc_core.hpp"
+#include "token_core.hpp"
 #include "swin.hpp"
 
 #include <memory>
@@ -166,19 +166,7 @@ SwinWs swin_ws(const effocr_swin* e, int B) {
 }
 
 int swin_chunk(const effocr_swin* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) c = (int)std::min<size_t>(SWIN_MAX_CHUNK, std::max<size_t>(1, SWIN_WS_BUDGET / swin_ws(e, 1).total));
-  return c < batch ? c : batch;
-}
-
-// One linear of the forward, out [M][N] = epilogue(X [M][K] . W [N][K]^T + bias): dense rows (ldx = ldw = K, ldo = ldr = N), the kernel
-// chosen by (precision, N, K) alone.  resid (EPI_BIAS_RESID only) may be out itself: the forward adds into the residual stream in place.
-int swin_linear(int prec, int epi, const void* X, const void* W, const float* bias, const float* resid, void* out, int64_t M, int N, int K,
-                hipStream_t s) {
-  GemmArgs g{};
-  g.X = X; g.ldx = K; g.W = W; g.ldw = K; g.bias = bias; g.out = out; g.ldo = N; g.M = (int)M; g.N = N; g.K = K;
-  if (epi == EPI_BIAS_RESID) { g.resid = resid; g.ldr = N; }
-  return gemm2_supported(prec, N, K) ? gemm2_nt(prec, epi, g, s) : gemm_nt(prec, epi, g, s);
+  return enc_default_chunk(e, batch, SWIN_WS_BUDGET, SWIN_MAX_CHUNK, [e](int B) { return swin_ws(e, B).total; });
 }
 
 // One sub-batch: patch_embed -> 4 stages of [patch merging] + blocks (LN1 -> qkv -> window attention -> proj + residual; LN2 -> fc1 + GELU
@@ -194,7 +182,9 @@ int swin_forward(const effocr_swin* e, const float* x, int B, float* emb, int l2
   int* status = reinterpret_cast<int*>(ws + w.status);
   int rc;
   auto lin = [&](const void* X, int K, size_t woff, size_t boff, void* out, int N, int epi, int64_t M) {
-    return swin_linear(prec, epi, X, wb + woff, F(boff), epi == EPI_BIAS_RESID ? xs : nullptr, out, M, N, K, s);
+    LinearExtras r{};
+    if (epi == EPI_BIAS_RESID) r.resid = xs;             // added into the residual stream in place
+    return dense_linear(prec, epi, X, K, wb + woff, F(boff), out, N, M, r, s);
   };
   if ((rc = swin_stem(x, B, e->img, F(e->stemw), F(e->stemb), F(e->stemlnw), F(e->stemlnb), e->st[0].C, SWIN_EPS, xs, s))) return rc;
   for (int i = 0; i < 4; ++i) {
@@ -279,9 +269,7 @@ SWIN_API int effocr_swin_forward(effocr_swin_t* enc, const float* x_dev, int bat
 }
 
 SWIN_API int effocr_swin_check_status(const effocr_swin_t* enc, const void* workspace_dev, void* stream) {   // SwinWs::status = offset 0
-  return enc_check_status("swin", enc, workspace_dev, stream,
-                          "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
-                          "input was not finite; use precision bf16 or fp32 for this checkpoint");
+  return enc_check_status("swin", enc, workspace_dev, stream, ENC_F16_OPERAND_OVERFLOW);
 }
 
 // ---- test entry points (tests/test_gpu_swin_ops.py): one launcher each, arguments checked before any launch ----------------------
@@ -354,5 +342,7 @@ SWIN_API int effocr_swin_op_linear(int precision, int epilogue, const void* x_de
   if (n % 128 || (k * prec_esize(precision)) % 128)
     return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_linear: n % 128 == 0 and rows of k elements a multiple of 128 bytes required");
   if (rows * std::max(n, k) >= (int64_t)1 << 31) return fail(EFFOCR_SWIN_EUNSUPPORTED, "swin_op_linear: rows * max(n, k) beyond 32-bit GEMM indices");
-  return swin_linear(precision, epilogue, x_dev, w_dev, bias_dev, resid_dev, out_dev, rows, n, k, S(stream));
+  LinearExtras r{};
+  if (epilogue == EPI_BIAS_RESID) r.resid = resid_dev;
+  return dense_linear(precision, epilogue, x_dev, k, w_dev, bias_dev, out_dev, n, rows, r, S(stream));
 }

@@ -3,7 +3,7 @@
 // compiles once more with hidden visibility) and the library's own error state.  All device memory is caller-owned; this file
 // allocates host memory only.
 #include "../../include/effocr_vit8.h"
-#include "enc_core.hpp"
+#include "token_core.hpp"
 #include "vit8.hpp"
 
 #include <memory>
@@ -18,7 +18,7 @@ constexpr float VIT8_EPS = 1e-6f;                        // timm's vision_transf
 constexpr size_t VIT8_WS_BUDGET = (size_t)1000 << 20;
 constexpr int VIT8_MAX_CHUNK = 256;
 
-struct BlockOff { size_t ln1w, ln1b, qkvw, qkvb, projw, projb, ln2w, ln2b, fc1w, fc1b, fc2w, fc2b; };
+using BlockOff = TokenBlockOff;
 
 }  // namespace
 }  // namespace effocr
@@ -57,12 +57,7 @@ void build_vit8(effocr_vit8* e) {
     e->add_param(q + "mlp.fc1.weight", (int64_t)4 * D * D); e->add_param(q + "mlp.fc1.bias", 4 * D);
     e->add_param(q + "mlp.fc2.weight", (int64_t)4 * D * D); e->add_param(q + "mlp.fc2.bias", D);
     BlockOff& L = e->blk[i];
-    L.ln1w = a.take((size_t)D * 4); L.ln1b = a.take((size_t)D * 4);
-    L.qkvw = a.take((size_t)3 * D * D * es); L.qkvb = a.take((size_t)3 * D * 4);
-    L.projw = a.take((size_t)D * D * es); L.projb = a.take((size_t)D * 4);
-    L.ln2w = a.take((size_t)D * 4); L.ln2b = a.take((size_t)D * 4);
-    L.fc1w = a.take((size_t)4 * D * D * es); L.fc1b = a.take((size_t)4 * D * 4);
-    L.fc2w = a.take((size_t)4 * D * D * es); L.fc2b = a.take((size_t)D * 4);
+    take_norm1_qkv(a, L, D, es); take_proj(a, L, D, es); take_mlp(a, L, D, es);
   }
   e->add_param("norm.weight", D); e->add_param("norm.bias", D);
   e->normw = a.take((size_t)D * 4); e->normb = a.take((size_t)D * 4);
@@ -72,46 +67,27 @@ void build_vit8(effocr_vit8* e) {
 // Packing: fp32 vectors and pos_embed as they are; linear weights [N][K] rounded once to the operand type; the cls row is
 // cls_token + pos_embed[0], added once here in fp32.
 void pack_vit8(const effocr_vit8* e, std::vector<char>& blob) {
-  auto f32 = [&](size_t off, const std::string& n) { const auto& v = e->P(n); put_f32(blob, off, v.data(), v.size()); };
-  auto op = [&](size_t off, const std::string& n) { const auto& v = e->P(n); put_op(blob, off, v.data(), v.size(), e->prec); };
+  const Packer p{e, blob};
   const int D = e->D;
   std::vector<float> c0(e->P("cls_token"));
   const std::vector<float>& pos = e->P("pos_embed");
   for (int d = 0; d < D; ++d) c0[d] += pos[d];
   put_f32(blob, e->cls0, c0.data(), c0.size());
-  f32(e->pos, "pos_embed");
-  op(e->patchw, "patch_embed.proj.weight"); f32(e->patchb, "patch_embed.proj.bias");
+  p.f32(e->pos, "pos_embed");
+  p.op(e->patchw, "patch_embed.proj.weight"); p.f32(e->patchb, "patch_embed.proj.bias");
   for (int i = 0; i < e->depth; ++i) {
     const std::string q = "blocks." + std::to_string(i) + ".";
-    const BlockOff& L = e->blk[i];
-    f32(L.ln1w, q + "norm1.weight"); f32(L.ln1b, q + "norm1.bias");
-    f32(L.ln2w, q + "norm2.weight"); f32(L.ln2b, q + "norm2.bias");
-    op(L.qkvw, q + "attn.qkv.weight"); f32(L.qkvb, q + "attn.qkv.bias");
-    op(L.projw, q + "attn.proj.weight"); f32(L.projb, q + "attn.proj.bias");
-    op(L.fc1w, q + "mlp.fc1.weight"); f32(L.fc1b, q + "mlp.fc1.bias");
-    op(L.fc2w, q + "mlp.fc2.weight"); f32(L.fc2b, q + "mlp.fc2.bias");
+    pack_token_block(p, e->blk[i], q);
+    p.f32(e->blk[i].qkvb, q + "attn.qkv.bias");
   }
-  f32(e->normw, "norm.weight"); f32(e->normb, "norm.bias");
+  p.f32(e->normw, "norm.weight"); p.f32(e->normb, "norm.bias");
 }
 
-// workspace of one sub-batch of B crops: status word, fp32 residual [B T][D], the operand buffer A (patch rows [B P][192], LayerNorm
-// and attention outputs [B T][D]) and the buffer Q of the qkv output [B T][3D] / the hidden [B T][4D] (never live at once).
-struct Vit8Ws { size_t status, x, a, q, total; };
-Vit8Ws vit8_ws(const effocr_vit8* e, int B) {
-  const size_t es = prec_esize(e->prec), M = (size_t)B * e->T, D = e->D;
-  Alloc a; Vit8Ws w;
-  w.status = a.take(256);                   // int32 status word at workspace offset 0 (effocr_vit8_check_status)
-  w.x = a.take(M * D * 4);
-  w.a = a.take(std::max(M * D, (size_t)B * (e->T - 1) * VIT8_PATCH_K) * es);
-  w.q = a.take(M * 4 * D * es);
-  w.total = a.off;
-  return w;
-}
+// workspace of one sub-batch of B crops: token_core.hpp's layout with patch rows [B P][192]
+TokenWs vit8_ws(const effocr_vit8* e, int B) { return token_ws(B, e->T, e->D, VIT8_PATCH_K, prec_esize(e->prec)); }
 
 int vit8_chunk(const effocr_vit8* e, int batch) {
-  int c = e->chunk;
-  if (c <= 0) c = (int)std::min<size_t>(VIT8_MAX_CHUNK, std::max<size_t>(1, VIT8_WS_BUDGET / vit8_ws(e, 1).total));
-  return c < batch ? c : batch;
+  return enc_default_chunk(e, batch, VIT8_WS_BUDGET, VIT8_MAX_CHUNK, [e](int B) { return vit8_ws(e, B).total; });
 }
 
 // One sub-batch: im2col -> patch GEMM (+ bias + pos_embed) into rows 1.. of every crop, cls row -> blocks (LN1 -> qkv -> streaming
@@ -119,32 +95,19 @@ int vit8_chunk(const effocr_vit8* e, int batch) {
 // (precision, N, K) alone and reduces K in a fixed order (no split-K); the attention kernel walks each crop's own keys: a crop's
 // embedding does not depend on B.
 int vit8_forward(const effocr_vit8* e, const float* x, int B, float* emb, int l2, char* ws, hipStream_t s) {
-  const Vit8Ws w = vit8_ws(e, B);
+  const TokenWs w = vit8_ws(e, B);
   const char* wb = e->wdev;
   const int prec = e->prec, D = e->D, T = e->T;
-  const int64_t M = (int64_t)B * T;
   auto F = [&](size_t off) { return reinterpret_cast<const float*>(wb + off); };
   float* xs = reinterpret_cast<float*>(ws + w.x);
   void* A = ws + w.a; void* Q = ws + w.q;
   int* status = reinterpret_cast<int*>(ws + w.status);
   int rc;
-  auto lin = [&](const void* X, int K, size_t woff, size_t boff, void* out, int N, int epi) {
-    GemmArgs g{};
-    g.X = X; g.ldx = K; g.W = wb + woff; g.ldw = K; g.bias = F(boff); g.out = out; g.ldo = N; g.M = (int)M; g.N = N; g.K = K;
-    if (epi == EPI_BIAS_RESID) { g.resid = xs; g.ldr = N; }
-    return gemm2_supported(prec, N, K) ? gemm2_nt(prec, epi, g, s) : gemm_nt(prec, epi, g, s);
-  };
   if ((rc = vit8_patch_embed(prec, x, B, e->img, D, wb + e->patchw, F(e->patchb), F(e->cls0), F(e->pos), A, xs, s))) return rc;
-  for (int i = 0; i < e->depth; ++i) {
-    const BlockOff& L = e->blk[i];
-    if ((rc = layernorm_rows(prec, xs, M, D, F(L.ln1w), F(L.ln1b), VIT8_EPS, A, s))) return rc;
-    if ((rc = lin(A, D, L.qkvw, L.qkvb, Q, 3 * D, EPI_BIAS))) return rc;
-    if ((rc = vit8_attention(prec, Q, B, T, e->heads, A, s))) return rc;
-    if ((rc = lin(A, D, L.projw, L.projb, xs, D, EPI_BIAS_RESID))) return rc;
-    if ((rc = layernorm_rows(prec, xs, M, D, F(L.ln2w), F(L.ln2b), VIT8_EPS, A, s))) return rc;
-    if ((rc = lin(A, D, L.fc1w, L.fc1b, Q, 4 * D, EPI_BIAS_GELU))) return rc;
-    if ((rc = lin(Q, 4 * D, L.fc2w, L.fc2b, xs, D, EPI_BIAS_RESID))) return rc;
-  }
+  const TokenRun run{prec, wb, (int64_t)B * T, D, VIT8_EPS, xs, A, Q, s};
+  if ((rc = token_blocks(run, e->blk, EPI_BIAS_RESID, [&](const BlockOff&, const void* qkv, void* out) {
+         return vit8_attention(prec, qkv, B, T, e->heads, out, s);
+       }))) return rc;
   return final_cls_norm(xs, B, T, D, F(e->normw), F(e->normb), VIT8_EPS, l2, 0, emb, status, s);
 }
 
@@ -201,7 +164,7 @@ VIT8_API int effocr_vit8_forward(effocr_vit8_t* enc, const float* x_dev, int bat
   const int rc = enc_forward_args("vit8", enc, x_dev, batch, emb_dev, workspace_dev, workspace_bytes, effocr_vit8_workspace_bytes(enc, batch));
   if (rc || batch == 0) return rc;
   const int chunk = vit8_chunk(enc, batch);
-  if ((int64_t)chunk * enc->T * 4 * enc->D >= (int64_t)1 << 31)
+  if (!token_index_ok(chunk, enc->T, enc->D))
     return fail(EFFOCR_VIT8_EUNSUPPORTED, "vit8_forward: chunk too large for 32-bit GEMM indices (effocr_vit8_set_chunk)");
   return enc_forward_chunks(enc, x_dev, batch, chunk, emb_dev, [&](const float* x, int crops, float* emb) {
     return vit8_forward(enc, x, crops, emb, l2_normalize, static_cast<char*>(workspace_dev), S(stream));
@@ -209,16 +172,11 @@ VIT8_API int effocr_vit8_forward(effocr_vit8_t* enc, const float* x_dev, int bat
 }
 
 VIT8_API int effocr_vit8_check_status(const effocr_vit8_t* enc, const void* workspace_dev, void* stream) {   // Vit8Ws::status = offset 0
-  return enc_check_status("vit8", enc, workspace_dev, stream,
-                          "forward: non-finite embedding — an f16 operand overflowed (a LayerNorm, attention or GELU output beyond 65504) or the "
-                          "input was not finite; use precision bf16 or fp32 for this checkpoint");
+  return enc_check_status("vit8", enc, workspace_dev, stream, ENC_F16_OPERAND_OVERFLOW);
 }
 
 VIT8_API int effocr_vit8_reset_status(const effocr_vit8_t* enc, void* workspace_dev, void* stream) {
-  if (!enc || !workspace_dev) return fail(EFFOCR_VIT8_EINVAL, "vit8_reset_status: NULL argument");
-  const hipError_t er = hipMemsetAsync(workspace_dev, 0, sizeof(int), S(stream));
-  if (er != hipSuccess) return fail(EFFOCR_VIT8_EHIP, std::string("vit8_reset_status: ") + hipGetErrorString(er));
-  return EFFOCR_VIT8_OK;
+  return enc_reset_status("vit8", enc, workspace_dev, stream);
 }
 
 VIT8_API int effocr_vit8_op_attn(const void* qkv_dev, int batch, int tokens, int heads, int dtype, void* out_dev, void* stream) {

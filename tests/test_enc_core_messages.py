@@ -1,6 +1,6 @@
-"""The four encoder-family libraries share their handle plumbing (effocr_amd/csrc/enc_core.hpp): the messages their entry points leave in
+"""The seven encoder-family libraries share their handle plumbing (effocr_amd/csrc/enc_core.hpp): the messages their entry points leave in
 last_error are pinned here byte for byte, as each family's own API file worded them before the plumbing was shared.  No GPU is needed:
-create and set_param touch host memory only, and upload refuses both cases below before it makes a device call."""
+create and set_param touch host memory only, and upload and reset_status refuse the cases below before they make a device call."""
 import ctypes
 
 import numpy as np
@@ -25,7 +25,17 @@ FAMILIES = {
     "effnet": ("efficientnet_b0", 32, "conv_stem.weight", 864, "bn2.running_var", 40, -1,
                "effnet_create: img_size must be a multiple of 32 in [32, 224]",
                "effnet_create: unsupported architecture 'nope' (efficientnet_b0, tf_efficientnet_b0)"),
+    "beit": ("beit_tiny_test", 32, "cls_token", 128, "fc_norm.bias", 40, -1,
+             "beit_create: img_size must be a multiple of 16 from 16 to 224",
+             "beit_create: unsupported architecture 'nope'"),
+    "vit8": ("vit8_tiny_test", 16, "cls_token", 128, "norm.bias", 12, -1,
+             "vit8_create: img_size must be a multiple of 8 from 8 to 224",
+             "vit8_create: unsupported architecture 'nope'"),
+    "bit": ("resnetv2_50x1_bitm", 32, "stem.conv.weight", 9408, "norm.bias", 40, -1,
+            "bit_create: img_size must be a positive multiple of 32",
+            "bit_create: unsupported architecture 'nope' (resnetv2_50x1_bitm, resnetv2_101x1_bitm)"),
 }
+RESET_STATUS = ["beit", "bit", "effnet", "vit8"]         # the families that export effocr_<family>_reset_status
 
 
 class _Family:
@@ -84,5 +94,20 @@ def test_set_param_and_upload_messages(fam):
             assert F.set_param(h, name.encode(), zp, numel) == 0, F.error()
         assert F.upload(h, dummy, nbytes) == -5
         assert F.error() == f"{fam}_upload: parameter '{last}' was never set"
+    finally:
+        F.destroy(h)
+
+
+@pytest.mark.parametrize("fam", RESET_STATUS)
+def test_reset_status_null_workspace(fam):
+    arch, img = FAMILIES[fam][:2]
+    F = _Family(fam)
+    rc, h = F.make(arch, img)
+    assert rc == 0, F.error()
+    try:
+        assert F.reset_status(h, None, None) == -1             # refused before any device call
+        assert F.error() == f"{fam}_reset_status: NULL argument"
+        assert F.reset_status(None, None, None) == -1
+        assert F.error() == f"{fam}_reset_status: NULL argument"
     finally:
         F.destroy(h)
