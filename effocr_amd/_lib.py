@@ -409,6 +409,42 @@ def vit8_lib():
     return _load_family(VIT8_SO_PATH, "vit8", VIT8_ABI_VERSION, _vit8_signatures(), "patch-8 ViT encoder")
 
 
+# libeffocr_yolov8.so (include/effocr_yolov8.h): the YOLOv8 localizers yolov8n / s / m / l / x (a builder, a 3x3 stem and a distribution
+# decode of its own; it carries its own copies of the implicit-GEMM convolution and of the YOLOv5 engine's data-movement kernels, hidden).
+# Letterbox and NMS stay the product library's.
+YOLOV8_SO_PATH = os.path.join(_HERE, "libeffocr_yolov8.so")
+YOLOV8_ABI_VERSION = 1     # == EFFOCR_YOLOV8_ABI_VERSION of include/effocr_yolov8.h
+
+
+def _yolov8_signatures():
+    c = ctypes
+    vp, i32, i64, sz = c.c_void_p, c.c_int, c.c_int64, c.c_size_t
+    return {f"effocr_yolov8_{k}": v for k, v in {
+        "abi_version": (i32, []),
+        "last_error": (c.c_char_p, []),
+        "create": (i32, [c.c_char_p, i32, i32, i32, c.POINTER(vp)]),
+        "destroy": (None, [vp]),
+        "num_params": (i32, [vp]),
+        "param_name": (c.c_char_p, [vp, i32]),
+        "param_numel": (i64, [vp, i32]),
+        "set_param": (i32, [vp, c.c_char_p, vp, i64]),
+        "weights_bytes": (sz, [vp]),
+        "upload": (i32, [vp, vp, sz]),
+        "set_option": (i32, [vp, c.c_char_p, i32]),
+        "num_predictions": (i64, [vp]),
+        "num_outputs": (i32, [vp]),
+        "workspace_bytes": (sz, [vp, i32]),
+        "forward": (i32, [vp, vp, i32, vp, vp, sz, vp]),
+    }.items()}
+
+
+YOLOV8_EXPORTS = tuple(sorted(_yolov8_signatures()))
+
+
+def yolov8_lib():
+    return _load_family(YOLOV8_SO_PATH, "yolov8", YOLOV8_ABI_VERSION, _yolov8_signatures(), "YOLOv8 localizer")
+
+
 head_check = _family_check("head")
 swin_check = _family_check("swin")
 resnet_check = _family_check("resnet")
@@ -417,6 +453,7 @@ effnet_check = _family_check("effnet")
 beit_check = _family_check("beit")
 bit_check = _family_check("bit")
 vit8_check = _family_check("vit8")
+yolov8_check = _family_check("yolov8")
 
 
 def check(rc, what="", handle=None):

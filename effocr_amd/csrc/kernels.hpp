@@ -220,6 +220,16 @@ int nms_yolo_batch(const float* pred, int B, int n, int nc, float conf_thres, fl
 int nms_yolo(const float* pred, int n, int nc, float conf_thres, float iou_thres, int max_det, int max_nms, float max_wh, int agnostic,
              float* out, int* count, void* ws, size_t ws_bytes, hipStream_t s);
 
+// yolov8.hip — the YOLOv8 localizer's own kernels (libeffocr_yolov8.so only)
+// stem Conv(3, cout, 3, 2) + bias + SiLU straight from NCHW: wt [27 taps (ky, kx, c)][wt_ld], channels in groups of 16, OW % 4 == 0;
+// out channels out_off .. +cout_st (a multiple of 16; weight rows and bias zero from cout on: the channel padding to 32)
+int stem3x3s2_nchw(const float* x, const float* wt, int wt_ld, const float* bias, float* out, int B, int H, int W, int OH, int OW, int out_ld, int out_off,
+                   int cout, int cout_st, hipStream_t s);
+// Detect decode of one level: box logits [B,ny,nx,box_ld] (channel 16 * side + bin), class logits [B,ny,nx,cls_ld] -> pred [B,total,5 + nc]
+// rows row0 + y * nx + x = (cx, cy, w, h, 1, sigmoid(cls))
+int yolov8_decode(const float* box, int box_ld, const float* cls, int cls_ld, float* pred, int B, int ny, int nx, int nc, float stride, int64_t total,
+                  int64_t row0, hipStream_t s);
+
 // convnext.hip — the ConvNeXt encoder's own kernels (fp32 channels-last residual stream [tokens][Cp], Cp = channels padded to 128;
 // the pointwise linears are gemm_nt / gemm2_nt).  Every kernel computes a token from that token's inputs alone, in a fixed order.
 // stem: 4x4/s4 conv (wt: [48 taps (c, ky, kx)][128] fp32) + channel LayerNorm over C0 <= 128 -> x [B*(S/4)^2][128] (pad channels 0)

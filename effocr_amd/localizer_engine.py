@@ -180,6 +180,123 @@ def yolov5_scale(state_dict):
     return scale
 
 
+# ultralytics YOLOv8 scales (yolov8.yaml `scales`): (depth_multiple, width_multiple, max_channels).  Written from the published yaml,
+# nn/modules and parse_model without an ultralytics install at hand: UNVERIFIED against a real checkpoint (DESIGN.md section 3 "YOLOv8");
+# the tables give the five published parameter counts (tests/test_yolov8_host.py).
+YOLOV8_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768), "l": (1.00, 1.00, 512), "x": (1.00, 1.25, 512)}
+YOLOV8_DFL_KEY = "model.22.dfl.conv.weight"
+YOLOV8_REG_MAX = 16
+
+
+def _yolov8_dims(scale):
+    """(channels(c), repeats(n)) of parse_model at ``scale``: make_divisible(min(c, max_channels) * width, 8) and max(round(n * depth), 1)."""
+    if scale not in YOLOV8_SCALES:
+        raise ValueError(f"unknown YOLOv8 scale {scale!r} (one of {', '.join(YOLOV8_SCALES)})")
+    depth, width, max_channels = YOLOV8_SCALES[scale]
+    return (lambda c: math.ceil(min(c, max_channels) * width / 8) * 8), (lambda n: max(round(n * depth), 1) if n > 1 else n)
+
+
+def yolov8_param_shapes(nc, scale="s"):
+    """{ultralytics key: shape} of YOLOv8<scale> (yolov8.yaml, ``scale`` in "nsmlx") with ``nc`` classes, in module order."""
+    ch, rep = _yolov8_dims(scale)
+    shapes = {}
+
+    def conv(name, c1, c2, k):
+        shapes[name + ".conv.weight"] = (c2, c1, k, k)
+        for s in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"{name}.bn.{s}"] = (c2,)
+
+    def c2f(name, c1, c2, n):
+        c = c2 // 2
+        conv(name + ".cv1", c1, 2 * c, 1)
+        conv(name + ".cv2", (2 + rep(n)) * c, c2, 1)
+        for i in range(rep(n)):
+            conv(f"{name}.m.{i}.cv1", c, c, 3)
+            conv(f"{name}.m.{i}.cv2", c, c, 3)
+
+    c64, c128, c256, c512, c1024 = ch(64), ch(128), ch(256), ch(512), ch(1024)
+    conv("model.0", 3, c64, 3)
+    conv("model.1", c64, c128, 3)
+    c2f("model.2", c128, c128, 3)
+    conv("model.3", c128, c256, 3)
+    c2f("model.4", c256, c256, 6)
+    conv("model.5", c256, c512, 3)
+    c2f("model.6", c512, c512, 6)
+    conv("model.7", c512, c1024, 3)
+    c2f("model.8", c1024, c1024, 3)
+    conv("model.9.cv1", c1024, c1024 // 2, 1)
+    conv("model.9.cv2", c1024 // 2 * 4, c1024, 1)
+    c2f("model.12", c1024 + c512, c512, 3)
+    c2f("model.15", c512 + c256, c256, 3)
+    conv("model.16", c256, c256, 3)
+    c2f("model.18", c256 + c512, c512, 3)
+    conv("model.19", c512, c512, 3)
+    c2f("model.21", c512 + c1024, c1024, 3)
+    c2, c3 = max(16, c256 // 4, 4 * YOLOV8_REG_MAX), max(c256, min(nc, 100))
+    for branch, cb, cout in (("cv2", c2, 4 * YOLOV8_REG_MAX), ("cv3", c3, nc)):
+        for l, cin in enumerate((c256, c512, c1024)):
+            conv(f"model.22.{branch}.{l}.0", cin, cb, 3)
+            conv(f"model.22.{branch}.{l}.1", cb, cb, 3)
+            shapes[f"model.22.{branch}.{l}.2.weight"] = (cout, cb, 1, 1)
+            shapes[f"model.22.{branch}.{l}.2.bias"] = (cout,)
+    shapes[YOLOV8_DFL_KEY] = (1, YOLOV8_REG_MAX, 1, 1)
+    return shapes
+
+
+def init_yolov8_state_dict(nc=2, scale="s", seed=0):
+    """Seeded random YOLOv8<scale> weights (there is no network to fetch a trained localizer): kaiming-uniform convolutions, BatchNorm with
+    non-trivial statistics, ultralytics' Detect.bias_init (box 1.0, class log(5 / nc / (640 / stride)^2)), the DFL constant 0 .. 15.  The last
+    box convolution has 32 x the kaiming gain: its 16-bin distributions are then peaked at bins that vary from side to side and anchor to
+    anchor (at unit gain every side is near 7.5 bins and every box the same size)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, shp in yolov8_param_shapes(nc, scale).items():
+        if k == YOLOV8_DFL_KEY:
+            sd[k] = torch.arange(YOLOV8_REG_MAX, dtype=torch.float32).view(shp)
+        elif k.endswith(".weight") and len(shp) == 4:
+            fan_in = shp[1] * shp[2] * shp[3]
+            bound = math.sqrt(3.0 / fan_in) * 1.2 * (32.0 if k.startswith("model.22.cv2.") and k.endswith(".2.weight") else 1.0)
+            sd[k] = (torch.rand(shp, generator=g) * 2 - 1) * bound
+        elif k.endswith("bn.weight"):
+            sd[k] = 1.0 + 0.2 * torch.randn(shp, generator=g)
+        elif k.endswith("bn.bias") or k.endswith("running_mean"):
+            sd[k] = 0.1 * torch.randn(shp, generator=g)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(shp, generator=g)
+        elif k.endswith(".bias"):                              # Detect.bias_init
+            l = int(k.split(".")[3])
+            b = 0.05 * torch.randn(shp, generator=g)
+            sd[k] = b + (1.0 if ".cv2." in k else math.log(5 / nc / (640 / STRIDES[l]) ** 2))
+    return sd
+
+
+def yolov8_scale(state_dict):
+    """The scale ("n" | "s" | "m" | "l" | "x") of an ultralytics YOLOv8 detection state dict: width from the stem's output channels
+    (``model.0.conv.weight``), depth from the number of bottlenecks in ``model.2.m``; every other key and shape must then match that
+    scale's table (which is what tells a wrong ``max_channels`` apart: m, l and x differ from a uniformly widened table only in their
+    deepest layers), and the DFL tensor must be the constant 0 .. 15.  ValueError names the mismatch."""
+    for key in (YOLOV8_DFL_KEY, "model.22.cv3.0.2.bias", "model.0.conv.weight"):
+        if key not in state_dict:
+            raise ValueError(f"state dict has no '{key}': not an ultralytics YOLOv8 detection model")
+    nc = int(state_dict["model.22.cv3.0.2.bias"].numel())
+    c0 = int(state_dict["model.0.conv.weight"].shape[0])
+    nm = len({k.split(".")[3] for k in state_dict if k.startswith("model.2.m.")})
+    by_width = [s for s in YOLOV8_SCALES if _yolov8_dims(s)[0](64) == c0]
+    if not by_width:
+        raise ValueError(f"model.0.conv.weight has {c0} output channels: no YOLOv8 scale has that width "
+                         f"({', '.join(f'{s}: {_yolov8_dims(s)[0](64)}' for s in YOLOV8_SCALES)})")
+    scale = by_width[0]
+    if _yolov8_dims(scale)[1](3) != nm:
+        raise ValueError(f"model.2.m has {nm} bottlenecks, but a stem of {c0} channels is YOLOv8{scale} with {_yolov8_dims(scale)[1](3)}")
+    bad = _shape_mismatches(state_dict, yolov8_param_shapes(nc, scale))
+    if bad:
+        raise ValueError(f"state dict does not match yolov8{scale}: " + "; ".join(bad[:6]) + (f" (+{len(bad) - 6} more)" if len(bad) > 6 else ""))
+    dfl = state_dict[YOLOV8_DFL_KEY].detach().to("cpu", torch.float32).reshape(-1)
+    if not torch.equal(dfl, torch.arange(YOLOV8_REG_MAX, dtype=torch.float32)):
+        raise ValueError(f"{YOLOV8_DFL_KEY} is not the constant 0 .. {YOLOV8_REG_MAX - 1}: the decode has that projection built in")
+    return scale
+
+
 def _load_state_dict(model_path):
     if isinstance(model_path, dict):
         sd = model_path
@@ -202,40 +319,55 @@ class HipLocalizer:
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
         self.precision = precision
         self.device = _lib.require_gpu(device)       # None / "cuda" = the current device
-        self._L = _lib.lib()
-        key = "model.24.m.0.bias"
-        if key not in state_dict:
-            raise ValueError(f"state dict has no '{key}': not an ultralytics YOLOv5 detection model")
-        no = int(state_dict[key].numel()) // 3
-        self.nc, self.no = no - 5, no
+        self._L = _lib.lib()                         # letterbox + NMS (and, here, the network)
+        self._N, self._ncheck = self._network_library()
         self.input_shape = (int(input_shape[0]), int(input_shape[1]))
-        self.scale = yolov5_scale(state_dict)
-        self.arch = "yolov5" + self.scale
-        if arch is not None and arch != self.arch:
-            raise ValueError(f"arch={arch!r}, but the state dict is {self.arch}")
+        self.nc, self.scale, self.arch = self._identify(state_dict, arch)
+        self.no = self.nc + 5
         self._h = ctypes.c_void_p()
-        _lib.check(self._L.effocr_localizer_create(self.arch.encode(), self.nc, self.input_shape[0], self.input_shape[1], ctypes.byref(self._h)),
-                   "effocr_localizer_create", self._L)
-        for i in range(self._L.effocr_localizer_num_params(self._h)):
-            name = self._L.effocr_localizer_param_name(self._h, i).decode()
+        self._ncheck(self._net("create")(self.arch.encode(), self.nc, self.input_shape[0], self.input_shape[1], ctypes.byref(self._h)),
+                     f"{self._PREFIX}_create")
+        for i in range(self._net("num_params")(self._h)):
+            name = self._net("param_name")(self._h, i).decode()
             t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
-            _lib.check(self._L.effocr_localizer_set_param(self._h, name.encode(), _lib.ptr(t), t.numel()), f"effocr_localizer_set_param({name})", self._L)
-        nbytes = int(self._L.effocr_localizer_weights_bytes(self._h))
+            self._ncheck(self._net("set_param")(self._h, name.encode(), _lib.ptr(t), t.numel()), f"{self._PREFIX}_set_param({name})")
+        nbytes = int(self._net("weights_bytes")(self._h))
         with torch.cuda.device(self.device):
             self._wblob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self._L.effocr_localizer_upload(self._h, _lib.ptr(self._wblob), nbytes), "effocr_localizer_upload", self._L)
+            self._ncheck(self._net("upload")(self._h, _lib.ptr(self._wblob), nbytes), f"{self._PREFIX}_upload")
         self.set_option("bf16_operands", 1 if precision == "bf16" else 0)
         # call_size_invariant=True: an image's predictions are bitwise the same in every batch size and position (no convolution
         # splits K; DESIGN.md "Call-size-invariant mode")
         self._call_size_invariant = False
         if call_size_invariant:
             self.set_option("call_size_invariant", 1)
-        self.num_predictions = int(self._L.effocr_localizer_num_predictions(self._h))
+        self.num_predictions = int(self._net("num_predictions")(self._h))
         self._ws = {}
         self._lock = threading.Lock()
 
+    _PREFIX = "effocr_localizer"                     # the network's entry points: <_PREFIX>_create ... <_PREFIX>_forward
+
+    def _network_library(self):
+        """(library that exports the network's entry points, its check(rc, what))."""
+        return self._L, (lambda rc, what: _lib.check(rc, what, self._L))
+
+    def _net(self, name):
+        return getattr(self._N, f"{self._PREFIX}_{name}")
+
+    @staticmethod
+    def _identify(state_dict, arch):
+        """(nc, scale, arch) of the checkpoint; ``arch`` (optional) must agree."""
+        key = "model.24.m.0.bias"
+        if key not in state_dict:
+            raise ValueError(f"state dict has no '{key}': not an ultralytics YOLOv5 detection model")
+        nc = int(state_dict[key].numel()) // 3 - 5
+        scale = yolov5_scale(state_dict)
+        if arch is not None and arch != "yolov5" + scale:
+            raise ValueError(f"arch={arch!r}, but the state dict is yolov5{scale}")
+        return nc, scale, "yolov5" + scale
+
     def set_option(self, name, value):
-        _lib.check(self._L.effocr_localizer_set_option(self._h, name.encode(), int(value)), "effocr_localizer_set_option", self._L)
+        self._ncheck(self._net("set_option")(self._h, name.encode(), int(value)), f"{self._PREFIX}_set_option")
         if name == "call_size_invariant":
             self._call_size_invariant = bool(value)
 
@@ -246,7 +378,7 @@ class HipLocalizer:
     def __del__(self):
         try:
             if getattr(self, "_h", None) is not None and self._h.value:
-                self._L.effocr_localizer_destroy(self._h)
+                self._net("destroy")(self._h)
                 self._h = ctypes.c_void_p()
         except Exception:
             pass
@@ -270,11 +402,11 @@ class HipLocalizer:
         pred = torch.empty((B, self.num_predictions, self.no), dtype=torch.float32, device=self.device)
         if B == 0:
             return pred
-        need = int(self._L.effocr_localizer_workspace_bytes(self._h, B))
+        need = int(self._net("workspace_bytes")(self._h, B))
         with self._lock, torch.cuda.device(self.device):
             ws = self._workspace("fwd", need)
-            _lib.check(self._L.effocr_localizer_forward(self._h, _lib.ptr(x), B, _lib.ptr(pred), _lib.ptr(ws), ws.numel(),
-                                                        _lib.current_stream(self.device)), "effocr_localizer_forward", self._L)
+            self._ncheck(self._net("forward")(self._h, _lib.ptr(x), B, _lib.ptr(pred), _lib.ptr(ws), ws.numel(), _lib.current_stream(self.device)),
+                         f"{self._PREFIX}_forward")
         return pred
 
     def letterbox(self, image, bgr=False, out=None):
@@ -347,13 +479,32 @@ class HipLocalizer:
         return out[: int(cnt.item())]
 
 
+class HipLocalizerV8(HipLocalizer):
+    """Device-resident YOLOv8 (n / s / m / l / x): the network is libeffocr_yolov8.so's (include/effocr_yolov8.h); its rows are
+    (cx, cy, w, h, 1.0, class scores) — a YOLOv5 row with a constant objectness — so ``letterbox``, ``nms_async`` and ``nms_batch_async``
+    are HipLocalizer's, on the product library."""
+
+    _PREFIX = "effocr_yolov8"
+
+    def _network_library(self):
+        return _lib.yolov8_lib(), _lib.yolov8_check
+
+    @staticmethod
+    def _identify(state_dict, arch):
+        scale = yolov8_scale(state_dict)
+        if arch is not None and arch != "yolov8" + scale:
+            raise ValueError(f"arch={arch!r}, but the state dict is yolov8{scale}")
+        return int(state_dict["model.22.cv3.0.2.bias"].numel()), scale, "yolov8" + scale
+
+
 class EffLocalizer:
 
     def __init__(self, model_path, iou_thresh=0.01, conf_thresh=0.30, vertical=False, num_cores=None, providers=None,
                  input_shape=(640, 640), model_backend='yolo', device=None, precision="fp32", arch=None, call_size_invariant=False):
         # precision (extension): "fp32" = fp32 MFMA operands (the oracle's arithmetic), "bf16" = bf16-rounded operands for every
         # convolution with an activation, fp32 accumulation and fp32 Detect heads (2-3x the network throughput)
-        # arch (extension): "yolov5n" ... "yolov5x" or None; the scale is read from the state dict and must agree (HipLocalizer)
+        # arch (extension): "yolov5n" ... "yolov5x", "yolov8n" ... "yolov8x" or None; family and scale are read from the state dict (a
+        # model.22.dfl.conv.weight key: YOLOv8) and must agree
         # num_cores / providers are ORT knobs (localizer_engine.py:17-23): accepted and ignored.
         if model_backend != 'yolo':
             raise NotImplementedError('Backend {} is not implemented'.format(model_backend))
@@ -361,8 +512,10 @@ class EffLocalizer:
         self._iou_thresh, self._conf_thresh, self._vertical = iou_thresh, conf_thresh, vertical
         self._input_shape = (int(input_shape[0]), int(input_shape[1]))
         self._model_backend = model_backend
-        self._eng_net = HipLocalizer(_load_state_dict(model_path), input_shape=self._input_shape, device=device, precision=precision,
-                                     arch=arch, call_size_invariant=call_size_invariant)
+        sd = _load_state_dict(model_path)
+        engine = HipLocalizerV8 if YOLOV8_DFL_KEY in sd else HipLocalizer      # the checkpoint says which network it is
+        self._eng_net = engine(sd, input_shape=self._input_shape, device=device, precision=precision, arch=arch,
+                               call_size_invariant=call_size_invariant)
 
     def __call__(self, imgs):
         return self.run(imgs)
