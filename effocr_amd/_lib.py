@@ -409,6 +409,29 @@ def vit8_lib():
     return _load_family(VIT8_SO_PATH, "vit8", VIT8_ABI_VERSION, _vit8_signatures(), "patch-8 ViT encoder")
 
 
+# libeffocr_levit.so (include/effocr_levit.h): the LeViT encoders levit_128s / levit_128 / levit_192 / levit_256 / levit_384 (attention with
+# narrow queries and keys, a per-head offset bias and a strided-query form, a 3x3 stem; it carries its own copies of the GEMMs, hidden).
+LEVIT_SO_PATH = os.path.join(_HERE, "libeffocr_levit.so")
+LEVIT_ABI_VERSION = 1     # == EFFOCR_LEVIT_ABI_VERSION of include/effocr_levit.h
+
+
+def _levit_signatures():
+    c = ctypes
+    vp, i32, i64 = c.c_void_p, c.c_int, c.c_int64
+    sig = _encoder_signatures("levit")
+    sig["effocr_levit_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_levit_op_attention"] = (i32, [vp, i64, i32, i32, vp, i64, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp])   # test entry points
+    sig["effocr_levit_op_stem_conv"] = (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, i32, vp])
+    return sig
+
+
+LEVIT_EXPORTS = tuple(sorted(_levit_signatures()))
+
+
+def levit_lib():
+    return _load_family(LEVIT_SO_PATH, "levit", LEVIT_ABI_VERSION, _levit_signatures(), "LeViT encoder")
+
+
 # libeffocr_yolov8.so (include/effocr_yolov8.h): the YOLOv8 localizers yolov8n / s / m / l / x (a builder, a 3x3 stem and a distribution
 # decode of its own; it carries its own copies of the implicit-GEMM convolution and of the YOLOv5 engine's data-movement kernels, hidden).
 # Letterbox and NMS stay the product library's.
@@ -454,6 +477,7 @@ beit_check = _family_check("beit")
 bit_check = _family_check("bit")
 vit8_check = _family_check("vit8")
 yolov8_check = _family_check("yolov8")
+levit_check = _family_check("levit")
 
 
 def check(rc, what="", handle=None):

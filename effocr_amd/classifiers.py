@@ -140,6 +140,10 @@ def AutoClassifierFactory(backend, modelpath, n_classes, precision=DEFAULT_PRECI
 
         @property
         def head(self):
+            if self._head is None and W.is_levit(self.model_name):
+                # two BatchNorm1d + Linear heads whose logits timm averages: folded on the host in float64 into one matrix
+                w, b = W.levit_fold_heads(self._sd)
+                self._head = HipClassifierHead(w, b, device=self._device)
             if self._head is None:
                 wk, bk = W.head_keys(self.model_name)
                 w = self._sd[wk]

@@ -52,6 +52,8 @@ class EffRecognizer:
         self.arch = arch or W.infer_arch(sd)
         if W.is_vit8(self.arch):
             img_size = W.vit8_img_size(sd)               # a patch-8 ViT's pos_embed rows fix the crop size
+        elif W.is_levit(self.arch):
+            img_size = W.levit_img_size(sd)              # a LeViT's attention_biases columns fix the crop size
         # call_size_invariant (extension): embs[i] bitwise independent of how the caller batches (HipEncoder)
         self._eng_net = make_encoder(self.arch, sd, img_size=img_size, precision=precision, device=device,
                                      call_size_invariant=call_size_invariant)

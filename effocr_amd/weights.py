@@ -152,6 +152,21 @@ VIT8_CFG = {
     "vit8_tiny_test": (128, 2, 2, 4),         # miniature used only by fast tests
 }
 VIT8_PATCH = 8
+LEVIT_CFG = {
+    # name: (widths, key_dim, heads, depths) — timm levit.py (the linear-token models): a four-convolution stem to img/16 tokens per side,
+    # three stages of attention + MLP blocks (mlp ratio 2, value width 2 x key_dim, BatchNorm after every linear, hardswish), between them
+    # a down-sampling attention (width / key_dim heads, value width 4 x key_dim, queries at the even rows and columns) + MLP; the pooled
+    # output is the mean of the final tokens; they run on libeffocr_levit.so.  levit_conv_*, levit_384_s8 and levit_512* are not supported.
+    "levit_128s": ((128, 256, 384), 16, (4, 6, 8), (2, 3, 4)),
+    "levit_128": ((128, 256, 384), 16, (4, 8, 12), (4, 4, 4)),
+    "levit_192": ((192, 288, 384), 32, (3, 5, 6), (4, 4, 4)),
+    "levit_256": ((256, 384, 512), 32, (4, 6, 8), (4, 4, 4)),
+    "levit_384": ((384, 512, 768), 32, (6, 9, 12), (4, 4, 4)),
+    "levit_tiny_test": ((128, 128, 128), 16, (2, 2, 4), (1, 1, 1)),       # miniatures used only by fast tests: key_dim 16 ...
+    "levit_tiny32_test": ((128, 192, 256), 32, (1, 3, 2), (1, 1, 1)),     # ... and key_dim 32 with a width that is no multiple of 128
+}
+LEVIT_SUPPORTED = ("levit_128s", "levit_128", "levit_192", "levit_256", "levit_384")
+LEVIT_BN_EPS = 1e-5
 MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
 MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
 PATCH = 16
@@ -271,7 +286,27 @@ def embed_dim(arch):
         return BIT_FEATURES
     if arch in VIT8_CFG:
         return VIT8_CFG[arch][0]
+    if arch in LEVIT_CFG:
+        return LEVIT_CFG[arch][0][-1]
+    _refuse_levit(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _refuse_levit(arch):
+    """A LeViT name this package does not build: NotImplementedError that lists the ones it does."""
+    if isinstance(arch, str) and arch.startswith("levit"):
+        raise NotImplementedError(f"unsupported LeViT {arch!r} (supported: {', '.join(LEVIT_SUPPORTED)}; levit_conv_*, levit_384_s8 and "
+                                  "levit_512* are not)")
+
+
+def is_levit(arch):
+    """levit_128s / levit_128 / levit_192 / levit_256 / levit_384 (and the two miniatures): the encoders that run on libeffocr_levit.so."""
+    return arch in LEVIT_CFG
+
+
+def levit_sub(R):
+    """Token grid per side after a stride-2 sub-sampling of the tokens at even rows and columns."""
+    return (R - 1) // 2 + 1
 
 
 def is_swin(arch):
@@ -336,7 +371,10 @@ HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bi
              "convnext": ("head.fc.weight", "head.fc.bias"), "mobilenetv3": ("classifier.weight", "classifier.bias"),
              "swin": ("head.fc.weight", "head.fc.bias"), "efficientnet": ("classifier.weight", "classifier.bias"),
              "beit": ("head.weight", "head.bias"), "bit": ("head.fc.weight", "head.fc.bias"),
-             "vit8": ("head.weight", "head.bias")}
+             "vit8": ("head.weight", "head.bias"),
+             # LeViT: two BatchNorm1d + Linear heads (head, head_dist) whose logits timm averages; these are the first head's linear
+             # (head_shapes lists all twelve keys, levit_fold_heads folds them into one matrix)
+             "levit": ("head.linear.weight", "head.linear.bias")}
 
 
 def _family(arch):
@@ -358,6 +396,9 @@ def _family(arch):
         return "bit"
     if arch in VIT8_CFG:
         return "vit8"
+    if arch in LEVIT_CFG:
+        return "levit"
+    _refuse_levit(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -373,6 +414,14 @@ def head_shapes(arch, num_classes):
     if num_classes:
         if num_classes < 0:
             raise ValueError(f"num_classes must be >= 0, got {num_classes}")
+        if arch in LEVIT_CFG:
+            D = embed_dim(arch)
+            for h in ("head", "head_dist"):
+                for leaf in ("weight", "bias", "running_mean", "running_var"):
+                    s[f"{h}.bn.{leaf}"] = (D,)
+                s[f"{h}.linear.weight"] = (int(num_classes), D)
+                s[f"{h}.linear.bias"] = (int(num_classes),)
+            return s
         wk, bk = head_keys(arch)
         s[wk] = (int(num_classes), embed_dim(arch)) + ((1, 1) if arch in BIT_CFG else ())
         s[bk] = (int(num_classes),)
@@ -485,7 +534,81 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _bit_shapes(arch)
     if arch in VIT8_CFG:
         return _vit8_shapes(arch, img_size)
+    if arch in LEVIT_CFG:
+        return _levit_shapes(arch, img_size)
+    _refuse_levit(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _levit_shapes(arch, img_size):
+    """timm >= 0.9's state-dict order for a Levit (levit.py; the key names are written from memory of that file, not verified against a
+    timm install): the stem, then per stage its downsample (stages 1 and 2) and its blocks.  A LinearNorm is ``linear.weight`` + ``bn.*``;
+    the length of an ``attention_biases`` row is the number of distinct (|dy|, |dx|) offsets of its key grid, R^2 — the crop size is part
+    of the shapes.  The derived ``attention_bias_idxs`` buffers and ``num_batches_tracked`` are not listed (ignored when present)."""
+    widths, kd, heads, depths = LEVIT_CFG[arch]
+    if img_size % 16 or not 32 <= img_size <= 224:
+        raise ValueError(f"{arch}: img_size must be a multiple of 16 from 32 to 224, got {img_size}")
+    s = OrderedDict()
+
+    def bn(p, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{p}.{leaf}"] = (c,)
+
+    def linear_norm(p, n, k):
+        s[p + ".linear.weight"] = (n, k)
+        bn(p + ".bn", n)
+
+    def mlp(p, d):
+        linear_norm(p + ".ln1", 2 * d, d)
+        linear_norm(p + ".ln2", d, 2 * d)
+
+    cin = 3
+    for i in range(4):
+        cout = widths[0] >> (3 - i)
+        s[f"stem.conv{i + 1}.linear.weight"] = (cout, cin, 3, 3)
+        bn(f"stem.conv{i + 1}.bn", cout)
+        cin = cout
+    R = img_size // 16
+    for st in range(3):
+        D = widths[st]
+        if st > 0:
+            din = widths[st - 1]
+            h = din // kd
+            p = f"stages.{st}.downsample.attn_downsample"
+            s[p + ".attention_biases"] = (h, R * R)
+            linear_norm(p + ".kv", h * 5 * kd, din)
+            linear_norm(p + ".q.ln", h * kd, din)
+            linear_norm(p + ".proj.ln", D, h * 4 * kd)
+            mlp(f"stages.{st}.downsample.mlp", D)
+            R = levit_sub(R)
+        for j in range(depths[st]):
+            p = f"stages.{st}.blocks.{j}."
+            s[p + "attn.attention_biases"] = (heads[st], R * R)
+            linear_norm(p + "attn.qkv", heads[st] * 4 * kd, D)
+            linear_norm(p + "attn.proj.ln", D, heads[st] * 2 * kd)
+            mlp(p + "mlp", D)
+    return s
+
+
+def levit_num_learnable(arch, img_size=224, num_classes=0):
+    """Learnable parameters (BN running statistics excluded) of the table, with timm's two optional classifier heads."""
+    return sum(math.prod(shp) for k, shp in param_shapes(arch, img_size, num_classes).items()
+               if not k.endswith(("running_mean", "running_var")))
+
+
+def levit_fold_heads(sd, eps=LEVIT_BN_EPS):
+    """timm's Levit classifier — the average of two ``BatchNorm1d + Linear`` heads (head, head_dist) — folded in float64 into one
+    weight [N, D] and bias [N] (float32) for the fp32 head library: logits = emb . W^T + b."""
+    sd = strip_prefix(sd)
+    Ws, bs = [], []
+    for h in ("head", "head_dist"):
+        g, beta = sd[h + ".bn.weight"].double(), sd[h + ".bn.bias"].double()
+        mean, var = sd[h + ".bn.running_mean"].double(), sd[h + ".bn.running_var"].double()
+        w, b = sd[h + ".linear.weight"].double(), sd[h + ".linear.bias"].double()
+        sc = g / torch.sqrt(var + eps)
+        Ws.append(w * sc[None, :])
+        bs.append(b + w @ (beta - mean * sc))
+    return ((Ws[0] + Ws[1]) / 2).float().contiguous(), ((bs[0] + bs[1]) / 2).float().contiguous()
 
 
 def _vit8_shapes(arch, img_size):
@@ -744,6 +867,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_bit(arch, seed, scale)
     if arch in VIT8_CFG:
         return _init_vit8(arch, seed, img_size, scale)
+    if arch in LEVIT_CFG:
+        return _init_levit(arch, seed, img_size, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -932,6 +1057,50 @@ def _init_beit(arch, seed, img_size, scale):
     return sd
 
 
+def _init_levit(arch, seed, img_size, scale):
+    """LeViT seeded init from a CPU Philox generator of its own.  scale="timm": trunc_normal(0.02) weights, BatchNorms at identity except
+    the last one of every residual branch (attn.proj.ln.bn, mlp.ln2.bn) at gamma 0, attention biases 0 — what timm's initialiser gives,
+    and a network whose residual branches and biases are all switched off.  scale="unit" (default): fan-in-scaled weights, attention
+    biases N(0, 1), BN gammas U(0.5, 1.5), betas and running means N(0, 0.1), running variances U(0.5, 1.5): no term is zero.  The last BN
+    of every residual branch draws its gamma from U(0.2, 0.5) instead: with gammas around 1 the up to 24 residual additions double the
+    stream's variance each (levit_128s reaches |x| ~ 60 and a 16-bit rounding error of 1.2e-2 against 3e-3).  The price is that every
+    branch, the attention's among them, adds a fraction of the stream: zeroing or transposing the biases moves a 32^2 - 64^2 embedding by
+    3 to 13 % depending on the seed and a 224^2 one by under 1 % — tests that rely on that sensitivity pick their seeds on the CPU
+    reference (tests/test_gpu_levit.py: CKPT_SEED)."""
+    if scale not in ("unit", "timm"):
+        raise ValueError(f"scale must be 'unit' or 'timm', got {scale!r}")
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x6C657669) % (1 << 63))
+    sd = OrderedDict()
+    for k, shp in _levit_shapes(arch, img_size).items():
+        leaf = k.rsplit(".", 1)[-1]
+        last = (".proj.ln.bn." in k or ".mlp.ln2.bn." in k) and ".attn_downsample." not in k
+        if leaf == "attention_biases":
+            v = torch.zeros(shp) if scale == "timm" else torch.randn(shp, generator=g, dtype=torch.float32)
+        elif len(shp) > 1:
+            if scale == "timm":
+                v = (torch.randn(shp, generator=g, dtype=torch.float32) * 0.02).clamp_(-0.04, 0.04)
+            else:
+                v = torch.randn(shp, generator=g, dtype=torch.float32) / math.sqrt(math.prod(shp[1:]))
+        elif scale == "timm":
+            if leaf in ("bias", "running_mean"):
+                v = torch.zeros(shp)
+            elif leaf == "running_var":
+                v = torch.ones(shp)
+            else:
+                v = torch.zeros(shp) if last else torch.ones(shp)
+        elif leaf == "running_var":
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+        elif leaf in ("bias", "running_mean"):
+            v = torch.randn(shp, generator=g, dtype=torch.float32) * 0.1
+        elif last:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) * 0.3 + 0.2
+        else:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+        sd[k] = v.contiguous()
+    return sd
+
+
 def _init_vit8(arch, seed, img_size, scale):
     """Patch-8 ViT seeded init from a CPU Philox generator of its own.  scale="timm": trunc_normal(0.02) linears, patch conv and
     pos_embed, cls token N(0, 1e-6), LayerNorms at identity, zero biases — what timm's initialiser gives.  scale="unit": fan-in-scaled
@@ -1033,6 +1202,21 @@ def init_head(arch, num_classes, seed=0, scale="unit"):
     g = torch.Generator(device="cpu")
     g.manual_seed((int(seed) * 0x9E3779B1 + 0x68656164) % (1 << 63))
     out = OrderedDict()
+    if arch in LEVIT_CFG:
+        # two BatchNorm1d + Linear heads: scale="unit" gives both non-trivial statistics and affine terms; scale="timm" BN at identity
+        for k, shp in head_shapes(arch, num_classes).items():
+            leaf = k.rsplit(".", 1)[-1]
+            if len(shp) == 2:
+                v = (torch.randn(shp, generator=g, dtype=torch.float32) * 0.02).clamp_(-0.04, 0.04) if scale == "timm" else \
+                    torch.randn(shp, generator=g, dtype=torch.float32) / math.sqrt(shp[1])
+            elif scale == "timm":
+                v = torch.ones(shp) if (leaf in ("weight", "running_var") and ".bn." in k) else torch.zeros(shp)
+            elif leaf == "running_var" or (leaf == "weight" and ".bn." in k):
+                v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+            else:
+                v = torch.randn(shp, generator=g, dtype=torch.float32) * 0.1
+            out[k] = v.contiguous()
+        return out
     (wk, wshape), (bk, bshape) = head_shapes(arch, num_classes).items()
     if scale == "timm":
         out[wk] = (torch.randn(wshape, generator=g, dtype=torch.float32) * 0.02).clamp_(-0.04, 0.04).contiguous()
@@ -1132,9 +1316,34 @@ def vit8_img_size(sd):
     return w * VIT8_PATCH
 
 
+def levit_img_size(sd):
+    """Crop size a LeViT checkpoint was built for: the first block's ``attention_biases`` has one column per (|dy|, |dx|) offset of the
+    (img_size / 16)^2 token grid."""
+    n = int(strip_prefix(sd)["stages.0.blocks.0.attn.attention_biases"].shape[-1])
+    r = math.isqrt(n)
+    if r * r != n or not 2 <= r <= 14:
+        raise ValueError(f"unsupported LeViT: attention_biases of {n} columns is not R^2 for a token grid 2 <= R <= 14")
+    return 16 * r
+
+
 def infer_arch(sd):
     """Guess the architecture of a checkpoint from its parameter shapes."""
     sd = strip_prefix(sd)
+    if "stem.conv1.linear.weight" in sd or "patch_embed.0.c.weight" in sd:
+        # LeViT: the shapes at the checkpoint's own crop size name the model
+        supported = "supported: " + ", ".join(LEVIT_SUPPORTED) + " in timm >= 0.9's key layout"
+        if "stem.conv1.linear.weight" not in sd:
+            raise ValueError(f"unsupported LeViT: the flat key layout of timm < 0.9 (patch_embed.0.c.weight, blocks.N.m.*) ({supported})")
+        qkv = sd.get("stages.0.blocks.0.attn.qkv.linear.weight")
+        if qkv is None or qkv.dim() != 2:
+            raise ValueError(f"unsupported LeViT: a convolutional variant (levit_conv_*) or an unknown layout ({supported})")
+        img = levit_img_size(sd)
+        for name in LEVIT_CFG:
+            want = param_shapes(name, img)
+            if all(k in sd and tuple(sd[k].shape) == shp for k, shp in want.items()):
+                return name
+        raise ValueError(f"unsupported LeViT: stem width {int(sd['stem.conv4.linear.weight'].shape[0])} with these block shapes matches "
+                         f"no supported model ({supported})")
     if "conv1.weight" in sd and "layer4.0.conv1.weight" in sd:
         # every ResNet has conv1 and layer4: the depth of layer3 and conv3 (Bottleneck) tell them apart
         depths = tuple(1 + max((int(k.split(".")[1]) for k in sd if k.startswith(f"layer{i}.")), default=-1) for i in range(1, 5))
