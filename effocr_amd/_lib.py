@@ -432,6 +432,35 @@ def levit_lib():
     return _load_family(LEVIT_SO_PATH, "levit", LEVIT_ABI_VERSION, _levit_signatures(), "LeViT encoder")
 
 
+# libeffocr_regnet.so (include/effocr_regnet.h): the RegNetX / RegNetY encoders regnetx_002 ... regnety_016 (a grouped 3x3 convolution, a
+# squeeze-excite gate, a ReLU stem, shortcut rows and a ReLU of its own, plus a hidden copy of libeffocr_mnv3.so's pointwise GEMM).
+REGNET_SO_PATH = os.path.join(_HERE, "libeffocr_regnet.so")
+REGNET_ABI_VERSION = 1     # == EFFOCR_REGNET_ABI_VERSION of include/effocr_regnet.h
+
+
+def _regnet_signatures():
+    c = ctypes
+    vp, i32, i64, sz = c.c_void_p, c.c_int, c.c_int64, c.c_size_t
+    sig = _encoder_signatures("regnet")
+    sig["effocr_regnet_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_regnet_op_tiles"] = (i32, [i32])                                                # test entry points
+    sig["effocr_regnet_op_gconv_weight_bytes"] = (sz, [i32, i32, i32])
+    sig["effocr_regnet_op_pack_gconv"] = (i32, [i32, i32, i32, vp, vp])
+    sig["effocr_regnet_op_gconv"] = (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp])
+    sig["effocr_regnet_op_se_gate"] = (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp])
+    sig["effocr_regnet_op_stem"] = (i32, [vp, i32, i32, vp, vp, vp, vp])
+    sig["effocr_regnet_op_gather2"] = (i32, [vp, i32, i32, i32, vp, vp])
+    sig["effocr_regnet_op_relu"] = (i32, [vp, i64, vp])
+    return sig
+
+
+REGNET_EXPORTS = tuple(sorted(_regnet_signatures()))
+
+
+def regnet_lib():
+    return _load_family(REGNET_SO_PATH, "regnet", REGNET_ABI_VERSION, _regnet_signatures(), "RegNet encoder")
+
+
 # libeffocr_yolov8.so (include/effocr_yolov8.h): the YOLOv8 localizers yolov8n / s / m / l / x (a builder, a 3x3 stem and a distribution
 # decode of its own; it carries its own copies of the implicit-GEMM convolution and of the YOLOv5 engine's data-movement kernels, hidden).
 # Letterbox and NMS stay the product library's.
@@ -478,6 +507,7 @@ bit_check = _family_check("bit")
 vit8_check = _family_check("vit8")
 yolov8_check = _family_check("yolov8")
 levit_check = _family_check("levit")
+regnet_check = _family_check("regnet")
 
 
 def check(rc, what="", handle=None):

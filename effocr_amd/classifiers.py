@@ -6,7 +6,7 @@
 before L2 normalisation, which is exactly the input of timm's head) followed by ``HipClassifierHead``: the head's
 ``nn.Linear`` in exact fp32 with the argmax fused behind it (libeffocr_head.so, include/effocr_head.h).
 
-Only the ``"timm"`` backend and the architectures ``AutoEncoderFactory`` supports are implemented; ``"hf"``, XcitDinoClassifier
+Only the ``"timm"`` backend and the architectures ``AutoEncoderFactory`` supports are implemented (the RegNets' head is ``head.fc``); ``"hf"``, XcitDinoClassifier
 and anything else raise NotImplementedError, as the reference's ``else`` branch does.
 """
 import ctypes

@@ -443,19 +443,31 @@ class LevitEncoder(_FamilyEncoder):
         self._status_call("reset_status")
 
 
+class RegNetEncoder(_FamilyEncoder):
+    """libeffocr_regnet.so: regnetx_002 / _004 / _006 / _008 / _016 and regnety_002 / _004 / _006 / _008 / _016 (and the miniatures
+    regnetx_mini8_test / regnetx_mini16_test / regnety_mini24_test) at any img_size that is a positive multiple of 32 (the stem is an fp32
+    conv; every BatchNorm is folded at upload).  The checkpoint does not fix the crop size.  Default sub-batch: a workspace under 1 GB, at
+    most 256 crops."""
+    _family, _label = "regnet", "RegNet"
+
+    def reset_status(self):
+        """Clear the current stream's status word without reading it (asynchronous)."""
+        self._status_call("reset_status")
+
+
 def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None, call_size_invariant=False):
     """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, ResNetEncoder (libeffocr_resnet.so) for resnet34 / resnet50,
     MobileNetV3Encoder (libeffocr_mnv3.so) for mobilenetv3_small_075 / _small_100 / _large_100, EfficientNetEncoder
     (libeffocr_effnet.so) for efficientnet_b0 / tf_efficientnet_b0, BeitEncoder (libeffocr_beit.so) for beit_base_patch16_224 /
     beitv2_base_patch16_224, BitEncoder (libeffocr_bit.so) for resnetv2_50x1_bitm / resnetv2_101x1_bitm, Vit8Encoder (libeffocr_vit8.so) for
     vit_small_patch8_224 / vit_base_patch8_224, LevitEncoder (libeffocr_levit.so) for levit_128s / levit_128 / levit_192 / levit_256 /
-    levit_384, HipEncoder (libeffocr_hip.so)
-    for every other architecture
+    levit_384, RegNetEncoder (libeffocr_regnet.so) for regnetx_002 ... regnetx_016 and regnety_002 ... regnety_016, HipEncoder
+    (libeffocr_hip.so) for every other architecture
     (mobilenetv3_small_050 among them).  ``call_size_invariant``: HipEncoder's mode of that name; the other engines have the property
     in every mode and ignore the keyword."""
     cls = (SwinEncoder if W.is_swin(arch) else ResNetEncoder if W.is_resnet_lib(arch) else MobileNetV3Encoder if W.is_mnv3_lib(arch)
            else EfficientNetEncoder if W.is_efficientnet(arch) else BeitEncoder if W.is_beit(arch) else BitEncoder if W.is_bit(arch)
-           else Vit8Encoder if W.is_vit8(arch) else LevitEncoder if W.is_levit(arch) else HipEncoder)
+           else Vit8Encoder if W.is_vit8(arch) else LevitEncoder if W.is_levit(arch) else RegNetEncoder if W.is_regnet(arch) else HipEncoder)
     return cls(arch, state_dict, img_size=img_size, precision=precision, device=device, call_size_invariant=call_size_invariant)
 
 
@@ -468,7 +480,9 @@ def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size
     ``mobilenetv3_large_100``, ``efficientnet_b0``, ``tf_efficientnet_b0``, ``beit_base_patch16_224``, ``beitv2_base_patch16_224``,
     ``resnetv2_50x1_bitm`` and ``resnetv2_101x1_bitm`` (the reference's ``bit`` encoder type; also under timm >= 0.9's ``_bit`` names),
     ``vit_small_patch8_224`` and ``vit_base_patch8_224`` (the fine-patch ViTs: 785 tokens per 224^2 crop),
-    ``levit_128s``, ``levit_128``, ``levit_192``, ``levit_256`` and ``levit_384`` (the cheap transformers: 0.3 to 2.4 GMAC per 224^2 crop)
+    ``levit_128s``, ``levit_128``, ``levit_192``, ``levit_256`` and ``levit_384`` (the cheap transformers: 0.3 to 2.4 GMAC per 224^2 crop),
+    ``regnetx_002``, ``regnetx_004``, ``regnetx_006``, ``regnetx_008``, ``regnetx_016``, ``regnety_002``, ``regnety_004``, ``regnety_006``,
+    ``regnety_008`` and ``regnety_016`` (the design-space CNNs with a grouped 3x3 per block: 0.2 to 1.6 GMAC per 224^2 crop)
     (the "hf" branch and XcitDinoEncoder are out
     of scope); anything else raises NotImplementedError exactly like the reference's ``else`` branch
     (encoders.py:93-95).

@@ -38,9 +38,12 @@ class IndexFlatIP:
 
     def __init__(self, d, device=None, screen="auto"):
         self.d = int(d)
+        # the kernels take dims that are multiples of 32: any other d (a RegNet's 368, 440, 528, 888, 912) is stored and searched with
+        # zero columns up to the next one — the same inner products; add / search / reconstruct_n / write_index speak d
+        self._dk = (self.d + 31) // 32 * 32
         self.device = _lib.require_gpu(device)
         self._L = _lib.lib()
-        self._xb = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
+        self._xb = torch.empty((0, self._dk), dtype=torch.float32, device=self.device)
         self._ws = {}                            # scratch per HIP stream: calls on different streams never share partial lists
         self.screen = screen                     # "auto" | True | False
         self.screen_overflows = 0                # screened searches that had to re-run exactly (candidate cap exceeded)
@@ -62,7 +65,10 @@ class IndexFlatIP:
             raise TypeError("expected a numpy array or torch tensor")
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError(f"expected shape [n,{self.d}], got {tuple(x.shape)}")
-        return x.to(self.device, torch.float32).contiguous()
+        x = x.to(self.device, torch.float32)
+        if self._dk != self.d:
+            x = torch.nn.functional.pad(x, (0, self._dk - self.d))
+        return x.contiguous()
 
     def add(self, x):
         x = self._as_dev(x)
@@ -70,7 +76,7 @@ class IndexFlatIP:
         self._drop_copies()
 
     def reset(self):
-        self._xb = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
+        self._xb = torch.empty((0, self._dk), dtype=torch.float32, device=self.device)
         self._drop_copies()
 
     def _drop_copies(self):
@@ -105,7 +111,7 @@ class IndexFlatIP:
                 self.screen = False
 
     def _use_screen(self, k, nq=None):
-        if self.screen is False or self.d % 64 != 0 or k > 32 or self.ntotal < max(k, 1):
+        if self.screen is False or self._dk % 64 != 0 or k > 32 or self.ntotal < max(k, 1):
             return False
         if self.screen is True:
             return True
@@ -116,9 +122,9 @@ class IndexFlatIP:
             return self.ntotal >= self.SCREEN_MIN_ROWS
         # round 4: for 17..128 queries the screening pass streams the bf16 index once per 64 queries (dims that are multiples of 192):
         # 1M x 384, 64 queries: see profiles/README.md — from 17 queries on it beats the exact fp32 stream, which is MFMA-bound there
-        if self.ntotal >= self.SCREEN_MIN_ROWS and self.d % 192 == 0 and self.d <= 768 and 16 < nq <= 128:
+        if self.ntotal >= self.SCREEN_MIN_ROWS and self._dk % 192 == 0 and self._dk <= 768 and 16 < nq <= 128:
             return True
-        stream_cap = 64 if self.d <= 384 else 32
+        stream_cap = 64 if self._dk <= 384 else 32
         if self._qs_ok(k):
             # round 5, the Q-stationary pooled screen (tools/knn_c2_time.py, same box): 10 k x 384 at 1024 queries 88 us (k = 10) / 51 us
             # (k = 1) against 130 / 115 us on the round-4 chain and 160 / 97 us exact; 1M x 384 at 256 / 1024 queries 0.36 / 0.87 ms
@@ -136,7 +142,7 @@ class IndexFlatIP:
     use_qs = True              # A/B: False = screening passes without the blocked copy (round-4 kernels)
 
     def _qs_ok(self, k):
-        return self.use_qs and self.d in self.QS_DIMS and k <= 16 and self.ntotal >= 1024
+        return self.use_qs and self._dk in self.QS_DIMS and k <= 16 and self.ntotal >= 1024
 
     def _screen_copy(self, rowmajor=True, blocked=False):
         """The bf16 copies of the rows a screening pass reads, built lazily per index change: row-major (the 128-query tile kernel,
@@ -147,16 +153,16 @@ class IndexFlatIP:
         with self._copy_lock, torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             if rowmajor and self._xb16 is None:
-                xb16 = torch.empty((self.ntotal, self.d), dtype=torch.bfloat16, device=self.device)
-                _lib.check(self._L.effocr_convert_bf16(_lib.ptr(self._xb), self.ntotal * self.d, _lib.ptr(xb16),
+                xb16 = torch.empty((self.ntotal, self._dk), dtype=torch.bfloat16, device=self.device)
+                _lib.check(self._L.effocr_convert_bf16(_lib.ptr(self._xb), self.ntotal * self._dk, _lib.ptr(xb16),
                                                        _lib.current_stream(self.device)), "effocr_convert_bf16", self._L)
                 ev = torch.cuda.Event()
                 ev.record(cur)
                 self._copy_ev["rowmajor"] = (ev, cur.cuda_stream)
                 self._xb16 = xb16
             if blocked and self._xblk is None:
-                xblk = torch.empty(int(self._L.effocr_bf16_blocked_bytes(self.ntotal, self.d)), dtype=torch.uint8, device=self.device)
-                _lib.check(self._L.effocr_convert_bf16_blocked(_lib.ptr(self._xb), self.ntotal, self.d, _lib.ptr(xblk),
+                xblk = torch.empty(int(self._L.effocr_bf16_blocked_bytes(self.ntotal, self._dk)), dtype=torch.uint8, device=self.device)
+                _lib.check(self._L.effocr_convert_bf16_blocked(_lib.ptr(self._xb), self.ntotal, self._dk, _lib.ptr(xblk),
                                                                _lib.current_stream(self.device)), "effocr_convert_bf16_blocked", self._L)
                 ev = torch.cuda.Event()
                 ev.record(cur)
@@ -173,7 +179,7 @@ class IndexFlatIP:
 
     def reconstruct_n(self, i0=0, n=None):
         n = self.ntotal - i0 if n is None else n
-        return self._xb[i0:i0 + n].cpu().numpy()
+        return self._xb[i0:i0 + n, :self.d].cpu().numpy()
 
     def remove_ids(self, ids):
         """Delete the given rows and compact (later rows shift down); returns the number removed."""
@@ -184,9 +190,9 @@ class IndexFlatIP:
         keep = np.ones(self.ntotal, dtype=bool)
         keep[ids] = False
         rows = torch.from_numpy(np.nonzero(keep)[0].astype(np.int64)).to(self.device)
-        dst = torch.empty((rows.numel(), self.d), dtype=torch.float32, device=self.device)
+        dst = torch.empty((rows.numel(), self._dk), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.effocr_gather_rows(_lib.ptr(self._xb), _lib.ptr(rows), rows.numel(), self.d,
+            _lib.check(self._L.effocr_gather_rows(_lib.ptr(self._xb), _lib.ptr(rows), rows.numel(), self._dk,
                                                   _lib.ptr(dst), _lib.current_stream(self.device)), "effocr_gather_rows", self._L)
         self._xb = dst
         self._drop_copies()
@@ -216,28 +222,28 @@ class IndexFlatIP:
         if self._use_screen(k, n):
             qs = self._qs_ok(k)
             # the streaming screen (17..128 queries against a large index) reads the row-major copy; everything else the blocked one
-            stream16 = self.ntotal >= self.SCREEN_MIN_ROWS and self.d % 192 == 0 and self.d <= 768 and 16 < n <= 128
+            stream16 = self.ntotal >= self.SCREEN_MIN_ROWS and self._dk % 192 == 0 and self._dk <= 768 and 16 < n <= 128
             self._screen_copy(rowmajor=stream16 or not qs, blocked=qs and not stream16)
-            need = int(self._L.effocr_knn_screen_workspace_bytes(n, self.ntotal, self.d, k))
+            need = int(self._L.effocr_knn_screen_workspace_bytes(n, self.ntotal, self._dk, k))
             with torch.cuda.device(self.device):
                 ws = self._workspace(need)
                 _lib.check(self._L.effocr_knn_ip_topk_screened2(_lib.ptr(q), n, _lib.ptr(self._xb),
                                                                 _lib.ptr(self._xb16 if (stream16 or not qs) else None),
-                                                                _lib.ptr(self._xblk if (qs and not stream16) else None), self.ntotal, self.d, k,
+                                                                _lib.ptr(self._xblk if (qs and not stream16) else None), self.ntotal, self._dk, k,
                                                                 self._xnorm_max, _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws),
                                                                 ws.numel(), _lib.current_stream(self.device)), "effocr_knn_ip_topk_screened", self._L)
                 if self._flag_pending is None:
-                    off = int(self._L.effocr_knn_screen_flag_offset(n, self.ntotal, self.d, k))
+                    off = int(self._L.effocr_knn_screen_flag_offset(n, self.ntotal, self._dk, k))
                     host = torch.empty(1, dtype=torch.int32).pin_memory()
                     host.copy_(ws[off:off + 4].view(torch.int32), non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(self.device))
                     self._flag_pending = (host, ev)
             return D, I
-        need = int(self._L.effocr_knn_workspace_bytes(n, self.ntotal, self.d, k))
+        need = int(self._L.effocr_knn_workspace_bytes(n, self.ntotal, self._dk, k))
         with torch.cuda.device(self.device):
             ws = self._workspace(need)
-            _lib.check(self._L.effocr_knn_ip_topk(_lib.ptr(q), n, _lib.ptr(self._xb), self.ntotal, self.d, k,
+            _lib.check(self._L.effocr_knn_ip_topk(_lib.ptr(q), n, _lib.ptr(self._xb), self.ntotal, self._dk, k,
                                                   _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws), ws.numel(),
                                                   _lib.current_stream(self.device)), "effocr_knn_ip_topk", self._L)
         return D, I
@@ -257,7 +263,7 @@ _FOURCC_IP = b"IxFI"
 
 
 def write_index(index, path):
-    xb = index._xb.cpu().numpy().astype("<f4", copy=False)
+    xb = np.ascontiguousarray(index._xb[:, :index.d].cpu().numpy().astype("<f4", copy=False))
     with open(path, "wb") as f:
         f.write(_FOURCC_IP)
         f.write(struct.pack("<iqqqBi", index.d, index.ntotal, 1 << 20, 1 << 20, 1, 0))

@@ -54,6 +54,7 @@ class EffRecognizer:
             img_size = W.vit8_img_size(sd)               # a patch-8 ViT's pos_embed rows fix the crop size
         elif W.is_levit(self.arch):
             img_size = W.levit_img_size(sd)              # a LeViT's attention_biases columns fix the crop size
+        # (a RegNet's name is inferred from its widths, depths and group width; its crop size stays the caller's img_size, as a ResNet's)
         # call_size_invariant (extension): embs[i] bitwise independent of how the caller batches (HipEncoder)
         self._eng_net = make_encoder(self.arch, sd, img_size=img_size, precision=precision, device=device,
                                      call_size_invariant=call_size_invariant)

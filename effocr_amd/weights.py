@@ -167,6 +167,32 @@ LEVIT_CFG = {
 }
 LEVIT_SUPPORTED = ("levit_128s", "levit_128", "levit_192", "levit_256", "levit_384")
 LEVIT_BN_EPS = 1e-5
+REGNET_CFG = {
+    # name: (w0, wa, wm, depth, group width, squeeze-excite) — timm regnet.py (the key names and this restatement are written from memory
+    # of that file, not verified against a timm install; the parameter counts equal timm's published ones): a 3x3/2 stem to 32 channels,
+    # four stages whose first block has stride 2, bottleneck ratio 1, a grouped 3x3 in every block; RegNetY adds squeeze-excite of width
+    # round(0.25 x the block's input width).  regnet_widths derives the stage widths and depths.  They run on libeffocr_regnet.so.
+    # regnetx_032 / regnety_032 and wider, regnetz_* and regnetv_* are not supported.
+    "regnetx_002": (24, 36.44, 2.49, 13, 8, False),
+    "regnetx_004": (24, 24.48, 2.54, 22, 16, False),
+    "regnetx_006": (48, 36.97, 2.24, 16, 24, False),
+    "regnetx_008": (56, 35.73, 2.28, 16, 16, False),
+    "regnetx_016": (80, 34.01, 2.25, 18, 24, False),
+    "regnety_002": (24, 36.44, 2.49, 13, 8, True),
+    "regnety_004": (48, 27.89, 2.09, 16, 8, True),
+    "regnety_006": (48, 32.54, 2.32, 15, 16, True),
+    "regnety_008": (56, 38.84, 2.40, 14, 16, True),
+    "regnety_016": (48, 20.71, 2.65, 27, 24, True),
+}
+REGNET_SUPPORTED = tuple(REGNET_CFG)
+REGNET_MINI = {
+    # miniatures used only by fast tests: (stage widths, depths, group width, squeeze-excite) given directly
+    "regnetx_mini8_test": ((8, 24, 40, 56), (1, 1, 2, 1), 8, False),
+    "regnetx_mini16_test": ((16, 32, 48, 80), (1, 1, 2, 1), 16, False),
+    "regnety_mini24_test": ((24, 48, 72, 120), (1, 1, 2, 1), 24, True),
+}
+REGNET_STEM = 32
+REGNET_BN_EPS = 1e-5
 MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
 MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
 PATCH = 16
@@ -288,7 +314,10 @@ def embed_dim(arch):
         return VIT8_CFG[arch][0]
     if arch in LEVIT_CFG:
         return LEVIT_CFG[arch][0][-1]
+    if is_regnet(arch):
+        return regnet_arch(arch)[0][-1]
     _refuse_levit(arch)
+    _refuse_regnet(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -302,6 +331,63 @@ def _refuse_levit(arch):
 def is_levit(arch):
     """levit_128s / levit_128 / levit_192 / levit_256 / levit_384 (and the two miniatures): the encoders that run on libeffocr_levit.so."""
     return arch in LEVIT_CFG
+
+
+def is_regnet(arch):
+    """regnetx_002 ... regnety_016 (and the three miniatures): the encoders that run on libeffocr_regnet.so."""
+    return arch in REGNET_CFG or arch in REGNET_MINI
+
+
+def _refuse_regnet(arch):
+    """A RegNet name this package does not build: NotImplementedError that lists the ones it does."""
+    if isinstance(arch, str) and arch.startswith("regnet"):
+        raise NotImplementedError(f"unsupported RegNet {arch!r} (supported: {', '.join(REGNET_SUPPORTED)}; regnetx_032 / regnety_032 and "
+                                  "wider, regnetz_* and regnetv_* are not)")
+
+
+def regnet_widths(w0, wa, wm, depth, group_width, q=8):
+    """timm regnet.py's width generation: u_j = w0 + wa j, k_j = round(log(u_j / w0) / log(wm)), w_j = round(w0 wm^k_j / q) q; runs of
+    equal widths are the stages; then every width becomes a multiple of its group width g = min(group_width, w) (bottleneck ratio 1).
+    Returns (stage widths, stage depths)."""
+    per_block = []
+    for j in range(depth):
+        k = round(math.log((w0 + wa * j) / w0) / math.log(wm))
+        per_block.append(int(round(w0 * wm ** k / q) * q))
+    widths, depths = [], []
+    for w in per_block:
+        if widths and widths[-1] == w:
+            depths[-1] += 1
+        else:
+            widths.append(w)
+            depths.append(1)
+    out = []
+    for w in widths:
+        g = min(group_width, w)
+        out.append(int(round(w / g) * g))
+    return tuple(out), tuple(depths)
+
+
+def regnet_arch(arch):
+    """(stage widths, stage depths, group width, squeeze-excite) of a RegNet name."""
+    if arch in REGNET_MINI:
+        return REGNET_MINI[arch]
+    w0, wa, wm, depth, gw, se = REGNET_CFG[arch]
+    widths, depths = regnet_widths(w0, wa, wm, depth, gw)
+    return widths, depths, gw, se
+
+
+def regnet_blocks(arch):
+    """The block list of a RegNet: dicts with key ("s1.b1"), cin, w, stride (2 in the first block of EVERY stage), gw, se (reduced width
+    round(0.25 x the block's INPUT width), 0 for RegNetX) and down (a downsample shortcut: the first block of each stage)."""
+    widths, depths, gw, se = regnet_arch(arch)
+    blocks, cin = [], REGNET_STEM
+    for si, (w, d) in enumerate(zip(widths, depths), start=1):
+        for bi in range(1, d + 1):
+            stride = 2 if bi == 1 else 1
+            blocks.append(dict(key=f"s{si}.b{bi}", cin=cin, w=w, stride=stride, gw=gw, se=int(round(cin * 0.25)) if se else 0,
+                               down=(stride != 1 or cin != w)))
+            cin = w
+    return blocks
 
 
 def levit_sub(R):
@@ -374,7 +460,9 @@ HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bi
              "vit8": ("head.weight", "head.bias"),
              # LeViT: two BatchNorm1d + Linear heads (head, head_dist) whose logits timm averages; these are the first head's linear
              # (head_shapes lists all twelve keys, levit_fold_heads folds them into one matrix)
-             "levit": ("head.linear.weight", "head.linear.bias")}
+             "levit": ("head.linear.weight", "head.linear.bias"),
+             # regnetx_* / regnety_*: the global average pool of the last block (final_conv is the identity)
+             "regnet": ("head.fc.weight", "head.fc.bias")}
 
 
 def _family(arch):
@@ -398,7 +486,10 @@ def _family(arch):
         return "vit8"
     if arch in LEVIT_CFG:
         return "levit"
+    if is_regnet(arch):
+        return "regnet"
     _refuse_levit(arch)
+    _refuse_regnet(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -536,8 +627,42 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _vit8_shapes(arch, img_size)
     if arch in LEVIT_CFG:
         return _levit_shapes(arch, img_size)
+    if is_regnet(arch):
+        return _regnet_shapes(arch)
     _refuse_levit(arch)
+    _refuse_regnet(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _regnet_shapes(arch):
+    """timm's state-dict order for a RegNet (regnet.py; the key names are written from memory of that file, not verified against a timm
+    install): the stem, then per block conv1, conv2, se (RegNetY), conv3 and, in the first block of a stage, downsample.  A ConvNormAct is
+    ``conv.weight`` + ``bn.*``; the squeeze-excite convolutions carry biases.  ``num_batches_tracked`` is not listed."""
+    s = OrderedDict()
+
+    def cna(p, cout, cin, k):
+        s[p + ".conv.weight"] = (cout, cin, k, k)
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{p}.bn.{leaf}"] = (cout,)
+    cna("stem", REGNET_STEM, 3, 3)
+    for b in regnet_blocks(arch):
+        p = b["key"]
+        cna(p + ".conv1", b["w"], b["cin"], 1)
+        cna(p + ".conv2", b["w"], b["gw"], 3)
+        if b["se"]:
+            s[p + ".se.fc1.weight"] = (b["se"], b["w"], 1, 1)
+            s[p + ".se.fc1.bias"] = (b["se"],)
+            s[p + ".se.fc2.weight"] = (b["w"], b["se"], 1, 1)
+            s[p + ".se.fc2.bias"] = (b["w"],)
+        cna(p + ".conv3", b["w"], b["w"], 1)
+        if b["down"]:
+            cna(p + ".downsample", b["w"], b["cin"], 1)
+    return s
+
+
+def regnet_num_learnable(arch, num_classes=0):
+    """Learnable parameters (BN running statistics excluded) of the table, with an optional classifier."""
+    return sum(math.prod(shp) for k, shp in param_shapes(arch, 224, num_classes).items() if not k.endswith(("running_mean", "running_var")))
 
 
 def _levit_shapes(arch, img_size):
@@ -869,6 +994,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_vit8(arch, seed, img_size, scale)
     if arch in LEVIT_CFG:
         return _init_levit(arch, seed, img_size, scale)
+    if is_regnet(arch):
+        return _init_regnet(arch, seed, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -1161,6 +1288,44 @@ def _init_bit(arch, seed, scale):
     return sd
 
 
+def _init_regnet(arch, seed, scale):
+    """RegNetX / RegNetY from a CPU Philox generator of their own.  Convolutions are kaiming-normal over their fan-in (std sqrt(2 / fan_in);
+    a grouped 3x3 has fan-in 9 x the group width), as the ResNets'.  scale="timm": BN at identity, conv3's gamma 0 (timm's zero_init_last),
+    squeeze-excite biases 0.  scale="unit": BN running means N(0, 0.1), running variances U(0.5, 1.5), betas N(0, 0.1), gammas U(0.5, 1.5)
+    except conv3's, U(0.2, 0.5) — so that the residual additions keep the stream within a few units, as a trained network's does — and
+    squeeze-excite weights N(0, 4 / fan_in), biases N(0, 0.5): gates spread over (0, 1) instead of sitting at 1/2."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x7265676E) % (1 << 63))
+    sd = OrderedDict()
+    for k, shp in _regnet_shapes(arch).items():
+        leaf = k.rsplit(".", 1)[-1]
+        last = ".conv3.bn." in k
+        if ".se." in k:
+            if len(shp) == 4:
+                v = torch.randn(shp, generator=g, dtype=torch.float32) * (math.sqrt(2.0 / shp[1]) if scale == "timm" else 2.0 / math.sqrt(shp[1]))
+            else:
+                v = torch.zeros(shp) if scale == "timm" else torch.randn(shp, generator=g, dtype=torch.float32) * 0.5
+        elif len(shp) == 4:
+            v = torch.randn(shp, generator=g, dtype=torch.float32) * math.sqrt(2.0 / (shp[1] * shp[2] * shp[3]))
+        elif scale == "timm":
+            if leaf in ("bias", "running_mean"):
+                v = torch.zeros(shp)
+            elif leaf == "running_var":
+                v = torch.ones(shp)
+            else:
+                v = torch.zeros(shp) if last else torch.ones(shp)
+        elif leaf == "running_var":
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+        elif leaf in ("bias", "running_mean"):
+            v = torch.randn(shp, generator=g, dtype=torch.float32) * 0.1
+        elif last:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) * 0.3 + 0.2
+        else:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5
+        sd[k] = v.contiguous()
+    return sd
+
+
 def _init_resnet(arch, seed, img_size, scale):
     """resnet34 / resnet50 from a CPU Philox generator of their own (resnet18 keeps the generic stream of init_state_dict).
     Convolutions are kaiming-normal (std sqrt(2 / fan_in)), as timm's.  scale="timm": BN at identity, with the last BN of every residual
@@ -1326,6 +1491,33 @@ def levit_img_size(sd):
     return 16 * r
 
 
+def _infer_regnet(sd):
+    """The RegNet a checkpoint holds: se.fc1 tells Y from X; the stage widths, the depths and conv2's second dimension (the group width)
+    pick the name, and every shape must then match.  Anything else is a ValueError that lists the supported names."""
+    supported = "supported: " + ", ".join(REGNET_SUPPORTED)
+    se = "s1.b1.se.fc1.weight" in sd
+    depths = tuple(max((int(k.split(".")[1][1:]) for k in sd if k.startswith(f"s{i}.b") and k.split(".")[1][1:].isdigit()), default=0)
+                   for i in range(1, 5))
+    widths = tuple(int(sd[f"s{i}.b1.conv1.conv.weight"].shape[0]) if f"s{i}.b1.conv1.conv.weight" in sd else -1 for i in range(1, 5))
+    c2 = sd.get("s1.b1.conv2.conv.weight")
+    gw = int(c2.shape[1]) if c2 is not None and c2.dim() == 4 else -1
+    kind = "RegNetY" if se else "RegNetX"
+    for name in tuple(REGNET_CFG) + tuple(REGNET_MINI):
+        w, d, g, s = regnet_arch(name)
+        if (w, d, g, s) != (widths, depths, gw, se):
+            continue
+        want = _regnet_shapes(name)
+        bad = [k for k, shp in want.items() if k not in sd or tuple(sd[k].shape) != shp]
+        extra = [k for k in sd if ".se." in k and k not in want]
+        if bad or extra:
+            raise ValueError(f"unsupported RegNet: widths {widths}, depths {depths} and group width {gw} are {name}'s, but "
+                             f"{(bad + extra)[0]} does not fit it ({supported})")
+        return name
+    if not se and any(".se." in k for k in sd):
+        kind = "RegNetX with squeeze-excite keys"
+    raise ValueError(f"unsupported RegNet: {kind}, widths {widths}, depths {depths}, group width {gw} ({supported})")
+
+
 def infer_arch(sd):
     """Guess the architecture of a checkpoint from its parameter shapes."""
     sd = strip_prefix(sd)
@@ -1344,6 +1536,8 @@ def infer_arch(sd):
                 return name
         raise ValueError(f"unsupported LeViT: stem width {int(sd['stem.conv4.linear.weight'].shape[0])} with these block shapes matches "
                          f"no supported model ({supported})")
+    if "s1.b1.conv1.conv.weight" in sd:
+        return _infer_regnet(sd)
     if "conv1.weight" in sd and "layer4.0.conv1.weight" in sd:
         # every ResNet has conv1 and layer4: the depth of layer3 and conv3 (Bottleneck) tell them apart
         depths = tuple(1 + max((int(k.split(".")[1]) for k in sd if k.startswith(f"layer{i}.")), default=-1) for i in range(1, 5))
