@@ -1,6 +1,7 @@
 // C ABI of libeffocr_convops.so — a TEST-ONLY library (DESIGN.md "Operator parity (convolutions and pools)").  Thin wrappers over the
-// convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, which this library compiles once more with
-// hidden visibility, so that tests/test_gpu_convops.py compares each kernel on its own with a float64 reference.  No product library
+// convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, over the ConvNeXt launchers of convnext.hip
+// and over the linears of convnext_forward (gemm.hip, gemm2.hip), which this library compiles once more with hidden visibility, so that
+// tests/test_gpu_convops.py and tests/test_gpu_convnext_ops.py compare each kernel on its own with a float64 reference.  No product library
 // exports these and no product code loads this one: libeffocr_hip.so is at its size cap (DESIGN.md "Library split").
 // All device pointers are caller-owned, `stream` is a hipStream_t (NULL = the default stream); every call returns 0 or a negative
 // EFFOCR_E* code (include/effocr_hip.h) whose message effocr_convops_last_error() holds for the calling thread.
@@ -8,10 +9,11 @@
 #include "enc_core.hpp"
 #include "resnet16.hpp"
 
+#include <algorithm>
 #include <string>
 
 #define CONVOPS_API extern "C" __attribute__((visibility("default")))
-#define EFFOCR_CONVOPS_ABI_VERSION 1
+#define EFFOCR_CONVOPS_ABI_VERSION 2
 
 namespace effocr {
 
@@ -121,4 +123,49 @@ CONVOPS_API int effocr_convops_avgpool16(int prec, const void* in, float* emb, i
   if (prec < 0 || prec > 2) return fail(EFFOCR_EINVAL, "convops_avgpool16: unknown element type");
   if (!in || !emb) return fail(EFFOCR_EINVAL, "convops_avgpool16: NULL argument");
   return rn_avgpool(prec, in, emb, B, HW, C, l2norm, status, static_cast<hipStream_t>(stream));
+}
+
+// ---- ConvNeXt (convnext.hip; layouts: kernels.hpp).  A shape the launcher refuses keeps the launcher's own code.
+CONVOPS_API int effocr_convops_cnx_stem(const float* img, int B, int S, const float* wt, const float* bias, const float* lnw, const float* lnb, int C0,
+                                        float* x, void* stream) {
+  if (!img || !wt || !bias || !lnw || !lnb || !x) return fail(EFFOCR_EINVAL, "convops_cnx_stem: NULL argument");
+  if (B < 0 || S < 0 || C0 < 0) return fail(EFFOCR_EINVAL, "convops_cnx_stem: negative size");
+  return cnx_stem(img, B, S, wt, bias, lnw, lnb, C0, x, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_cnx_dwconv_ln(int prec, const float* x, int B, int H, int W, int C, int Cp, const float* w, const float* bias,
+                                             const float* lnw, const float* lnb, void* out, void* stream) {
+  if (!x || !w || !bias || !lnw || !lnb || !out) return fail(EFFOCR_EINVAL, "convops_cnx_dwconv_ln: NULL argument");
+  if (B < 0 || H < 1 || W < 1 || C < 1 || Cp < 1) return fail(EFFOCR_EINVAL, "convops_cnx_dwconv_ln: bad shape");
+  return cnx_dwconv_ln(prec, x, B, H, W, C, Cp, w, bias, lnw, lnb, out, static_cast<hipStream_t>(stream));
+}
+CONVOPS_API int effocr_convops_cnx_ln_s2d(int prec, const float* x, int B, int H, int W, int C, int Cp, const float* lnw, const float* lnb, void* out,
+                                          void* stream) {
+  if (!x || !lnw || !lnb || !out) return fail(EFFOCR_EINVAL, "convops_cnx_ln_s2d: NULL argument");
+  if (B < 0 || H < 1 || W < 1 || C < 1 || Cp < 1) return fail(EFFOCR_EINVAL, "convops_cnx_ln_s2d: bad shape");
+  return cnx_ln_s2d(prec, x, B, H, W, C, Cp, lnw, lnb, out, static_cast<hipStream_t>(stream));
+}
+// status: optional device int, ORed with 1 on a non-finite embedding
+CONVOPS_API int effocr_convops_cnx_head(const float* x, int B, int HW, int C, int Cp, const float* lnw, const float* lnb, int l2norm, float* emb,
+                                        int* status, void* stream) {
+  if (!x || !lnw || !lnb || !emb) return fail(EFFOCR_EINVAL, "convops_cnx_head: NULL argument");
+  if (B < 0 || HW < 0 || C < 1 || Cp < 1) return fail(EFFOCR_EINVAL, "convops_cnx_head: bad shape");
+  return cnx_head(x, B, HW, C, Cp, lnw, lnb, l2norm, emb, status, static_cast<hipStream_t>(stream));
+}
+// A linear of convnext_forward, dispatched as its `lin` lambda does (api.hip): gemm2_nt where gemm2_supported, gemm_nt otherwise.  Dense rows
+// (ldx = ldw = k, ldo = ldr = n).  epilogue: 1 bias + GELU (out in the operand type), 5 bias (fp32 out), 4 fp32 out = resid + scale[n] (acc +
+// bias[n]), resid may be out.
+CONVOPS_API int effocr_convops_linear(int precision, int epilogue, const void* x, const void* w, const float* bias, const float* resid,
+                                      const float* scale, void* out, int m, int n, int k, void* stream) {
+  if (precision != PREC_BF16 && precision != PREC_FP16 && precision != PREC_FP32) return fail(EFFOCR_EINVAL, "convops_linear: unknown precision");
+  if (epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_F32 && epilogue != EPI_BIAS_SCALE_RESID)
+    return fail(EFFOCR_EINVAL, "convops_linear: unknown epilogue (1 bias + GELU, 4 bias, layer scale + residual, 5 bias with fp32 output)");
+  if (!x || !w || !bias || !out) return fail(EFFOCR_EINVAL, "convops_linear: NULL argument");
+  if (epilogue == EPI_BIAS_SCALE_RESID && (!resid || !scale)) return fail(EFFOCR_EINVAL, "convops_linear: epilogue 4 needs resid and scale");
+  if (m < 0 || n < 1 || k < 1) return fail(EFFOCR_EINVAL, "convops_linear: bad shape");
+  if ((int64_t)m * std::max(n, k) >= (int64_t)1 << 31) return fail(EFFOCR_EUNSUPPORTED, "convops_linear: m * max(n, k) beyond 32-bit GEMM indices");
+  GemmArgs g{};
+  g.X = x; g.ldx = k; g.W = w; g.ldw = k; g.bias = bias; g.out = out; g.ldo = n; g.M = m; g.N = n; g.K = k;
+  if (epilogue == EPI_BIAS_SCALE_RESID) { g.resid = resid; g.ldr = n; g.scale = scale; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return gemm2_supported(precision, n, k) ? gemm2_nt(precision, epilogue, g, s) : gemm_nt(precision, epilogue, g, s);
 }

@@ -1,5 +1,6 @@
 """ctypes binding of effocr_amd/libeffocr_convops.so, the TEST-ONLY operator library (csrc/convops_api.hip): thin wrappers over the
-convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip.  `make` builds it next to the product
+convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, the ConvNeXt launchers of convnext.hip and
+the linears of convnext_forward (gemm.hip, gemm2.hip).  `make` builds it next to the product
 libraries (``__graft_entry__.build()``); a missing library is an error here — no skip, no fallback."""
 
 import ctypes
@@ -7,8 +8,9 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO_PATH = os.path.join(ROOT, "effocr_amd", "libeffocr_convops.so")
-ABI_VERSION = 1
+ABI_VERSION = 2
 PREC_BF16, PREC_FP16, PREC_FP32 = 0, 1, 2
+PREC = {"bf16": PREC_BF16, "fp16": PREC_FP16, "fp32": PREC_FP32}
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 
 _c = ctypes
@@ -34,6 +36,11 @@ SIGNATURES = {
     "effocr_convops_im2col16": (_i, [_i, _vp, _vp] + [_i] * 5 + [_vp]),                    # prec, x, col, B, H, W, OH, OW
     "effocr_convops_maxpool16": (_i, [_i, _vp, _vp] + [_i] * 6 + [_vp]),                   # prec, in, out, B, H, W, C, OH, OW
     "effocr_convops_avgpool16": (_i, [_i, _vp, _vp] + [_i] * 4 + [_vp, _vp]),              # prec, in, emb, B, HW, C, l2norm, status
+    "effocr_convops_cnx_stem": (_i, [_vp, _i, _i] + [_vp] * 4 + [_i, _vp, _vp]),           # img, B, S, wt, bias, lnw, lnb, C0, x
+    "effocr_convops_cnx_dwconv_ln": (_i, [_i, _vp] + [_i] * 5 + [_vp] * 6),                # prec, x, B, H, W, C, Cp, w, bias, lnw, lnb, out
+    "effocr_convops_cnx_ln_s2d": (_i, [_i, _vp] + [_i] * 5 + [_vp] * 4),                   # prec, x, B, H, W, C, Cp, lnw, lnb, out
+    "effocr_convops_cnx_head": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _i, _vp, _vp, _vp]),     # x, B, HW, C, Cp, lnw, lnb, l2norm, emb, status
+    "effocr_convops_linear": (_i, [_i, _i] + [_vp] * 6 + [_i] * 3 + [_vp]),                # precision, epilogue, x, w, bias, resid, scale, out, m, n, k
 }
 EXPORTS = sorted(SIGNATURES)
 

@@ -85,18 +85,20 @@ def ln64(x, g, b, eps=EPS, stats=None):
     return (x - mean) / torch.sqrt(var + eps) * g.double() + b.double()
 
 
-def ln_bound(x, ex, g, b):
-    """(y, ey): float64 LayerNorm of x and the bound on the kernel's fp32 result before its store, x known to within ex."""
+def ln_bound(x, ex, g, b, eps=EPS):
+    """(y, ey): float64 LayerNorm of x and the bound on the kernel's fp32 result before its store, x known to within ex.
+    eps: the kernel's epsilon (Swin's 1e-5 by default; tests/convnext_ops_ref.py passes ConvNeXt's 1e-6).  LN_DEPTH = 20 also holds for
+    convnext.hip's seg_layernorm, whose tree is 2 levels in the thread + 5 in the half + at most 6 halves in order = 13 deep."""
     x, g, b = x.double(), g.double(), b.double()
     mean = x.mean(-1, keepdim=True)
     em = ex.mean(-1, keepdim=True) + gamma(LN_DEPTH) * x.abs().mean(-1, keepdim=True) + 2 * U * mean.abs()
     d = x - mean
     ed = ex + em + U * d.abs()
     var = (d * d).mean(-1, keepdim=True)
-    ev = gamma(LN_DEPTH + 3) * var + (2 * d.abs() * ed + ed * ed).mean(-1, keepdim=True) + 2 * U * (var + EPS)
-    assert bool((ev < 0.5 * (var + EPS)).all()), "LayerNorm data too ill-conditioned for a bound"
-    rstd = 1 / torch.sqrt(var + EPS)
-    er = torch.maximum(1 / torch.sqrt(var + EPS - ev) - rstd, rstd - 1 / torch.sqrt(var + EPS + ev)) + 4 * U * rstd
+    ev = gamma(LN_DEPTH + 3) * var + (2 * d.abs() * ed + ed * ed).mean(-1, keepdim=True) + 2 * U * (var + eps)
+    assert bool((ev < 0.5 * (var + eps)).all()), "LayerNorm data too ill-conditioned for a bound"
+    rstd = 1 / torch.sqrt(var + eps)
+    er = torch.maximum(1 / torch.sqrt(var + eps - ev) - rstd, rstd - 1 / torch.sqrt(var + eps + ev)) + 4 * U * rstd
     y = d * rstd * g + b
     ey = g.abs() * (ed * rstd + d.abs() * er + ed * er + 2 * U * d.abs() * rstd) + U * y.abs()
     return y, ey
@@ -149,32 +151,32 @@ def _stem_conv(x, w, b):
     return y.permute(0, 2, 3, 1).reshape(-1, w.shape[0])
 
 
-def stem_ref(d):
-    return ln64(_stem_conv(d["x"], d["w"], d["b"]), d["lnw"], d["lnb"])
+def stem_ref(d, eps=EPS):
+    return ln64(_stem_conv(d["x"], d["w"], d["b"]), d["lnw"], d["lnb"], eps)
 
 
-def stem_bound(d):
+def stem_bound(d, eps=EPS):
     ec = gamma(49) * _stem_conv(d["x"].abs(), d["w"].abs(), d["b"].abs())       # 48 FMAs on top of the bias
-    y, ey = ln_bound(_stem_conv(d["x"], d["w"], d["b"]), ec, d["lnw"], d["lnb"])
+    y, ey = ln_bound(_stem_conv(d["x"], d["w"], d["b"]), ec, d["lnw"], d["lnb"], eps)
     return ey + TINY32
 
 
-def stem_f32(d):
+def stem_f32(d, eps=EPS):
     C0 = d["w"].shape[0]
     y = F.conv2d(d["x"], d["w"], d["b"], stride=4).permute(0, 2, 3, 1).reshape(-1, C0)
-    return F.layer_norm(y, (C0,), d["lnw"], d["lnb"], EPS)
+    return F.layer_norm(y, (C0,), d["lnw"], d["lnb"], eps)
 
 
-def stem_mutants(d):
+def stem_mutants(d, eps=EPS):
     C0 = d["w"].shape[0]
     conv = _stem_conv(d["x"], d["w"], d["b"])
-    out = {"ky_kx_swapped": ln64(_stem_conv(d["x"], d["w"].transpose(2, 3), d["b"]), d["lnw"], d["lnb"]),
+    out = {"ky_kx_swapped": ln64(_stem_conv(d["x"], d["w"].transpose(2, 3), d["b"]), d["lnw"], d["lnb"], eps),
            "channel_major_taps": ln64(_stem_conv(d["x"], pack_stem(d)[0].flatten().view(128, 48)[:C0].reshape(C0, 3, 4, 4), d["b"]),
-                                      d["lnw"], d["lnb"]),
-           "bias_after_norm": ln64(_stem_conv(d["x"], d["w"], None), d["lnw"], d["lnb"]) + d["b"].double()}
+                                      d["lnw"], d["lnb"], eps),
+           "bias_after_norm": ln64(_stem_conv(d["x"], d["w"], None), d["lnw"], d["lnb"], eps) + d["b"].double()}
     if C0 < 128:
         p = pad_cols(conv, 128)
-        out["norm_over_128"] = ln64(conv, d["lnw"], d["lnb"], stats=(p.mean(-1, keepdim=True), p.var(-1, unbiased=False, keepdim=True)))
+        out["norm_over_128"] = ln64(conv, d["lnw"], d["lnb"], eps, stats=(p.mean(-1, keepdim=True), p.var(-1, unbiased=False, keepdim=True)))
     return out
 
 
@@ -459,8 +461,11 @@ def head_bound(d, l2):
     y, ey = ln_bound(d["x"], torch.zeros_like(d["x"], dtype=torch.float64), d["lnw"], d["lnb"])
     m = y.mean(1)
     e = (ey.sum(1) + gamma(HW) * y.abs().sum(1)) / HW + 2 * U * m.abs()         # HW adds in order, one division
-    if not l2:
-        return e + TINY32
+    return l2_bound(m, e) if l2 else e + TINY32
+
+
+def l2_bound(m, e):
+    """Bound behind x / max(||x||, 1e-12) of the rows of m, known to within e (the sum of squares runs on the LayerNorm tree)."""
     ss = (m * m).sum(1, keepdim=True)
     ess = (2 * m.abs() * e + e * e).sum(1, keepdim=True) + gamma(LN_DEPTH + 2) * ss
     n = torch.sqrt(ss).clamp_min(1e-12)

@@ -4,6 +4,7 @@ for every real-valued geometry; and the exact-data premise holds (fp32 accumulat
 
 import ctypes
 import dataclasses
+import subprocess
 
 import pytest
 import torch
@@ -24,7 +25,9 @@ def test_library_loads_and_exports_every_wrapper():
     raw = ctypes.CDLL(CL.SO_PATH)
     for name in CL.EXPORTS:
         assert hasattr(raw, name), f"{name} is not exported"
-    assert len(CL.EXPORTS) == 17
+    assert len(CL.EXPORTS) == 22
+    out = subprocess.run(["nm", "-D", "--defined-only", CL.SO_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == CL.EXPORTS      # no other function leaves the library
     assert CL.last_dispatch() == (0, 0)
 
 
