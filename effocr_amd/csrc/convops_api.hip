@@ -1,7 +1,8 @@
 // C ABI of libeffocr_convops.so — a TEST-ONLY library (DESIGN.md "Operator parity (convolutions and pools)").  Thin wrappers over the
-// convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, over the ConvNeXt launchers of convnext.hip
-// and over the linears of convnext_forward (gemm.hip, gemm2.hip), which this library compiles once more with hidden visibility, so that
-// tests/test_gpu_convops.py and tests/test_gpu_convnext_ops.py compare each kernel on its own with a float64 reference.  No product library
+// convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, over the ConvNeXt launchers of convnext.hip,
+// over the linears of convnext_forward (gemm.hip, gemm2.hip) and over the non-GEMM launchers of the ViT path (patch.hip, vit_ops.hip,
+// qkvattn.hip: effocr_convops_vit_*), which this library compiles once more with hidden visibility, so that tests/test_gpu_convops.py,
+// tests/test_gpu_convnext_ops.py and tests/test_gpu_vit_ops.py compare each kernel on its own with a float64 reference.  No product library
 // exports these and no product code loads this one: libeffocr_hip.so is at its size cap (DESIGN.md "Library split").
 // All device pointers are caller-owned, `stream` is a hipStream_t (NULL = the default stream); every call returns 0 or a negative
 // EFFOCR_E* code (include/effocr_hip.h) whose message effocr_convops_last_error() holds for the calling thread.
@@ -13,11 +14,13 @@
 #include <string>
 
 #define CONVOPS_API extern "C" __attribute__((visibility("default")))
-#define EFFOCR_CONVOPS_ABI_VERSION 2
+#define EFFOCR_CONVOPS_ABI_VERSION 3
 
 namespace effocr {
 
 extern thread_local int convops_last_nw, convops_last_ksplit;   // resnet.hip under -DEFFOCR_CONVOPS
+extern thread_local int convops_patch_dw, convops_patch_grid;   // patch.hip, likewise
+extern thread_local int convops_qa_launches, convops_qa_last[2][6];   // qkvattn.hip, likewise
 
 }  // namespace effocr
 
@@ -168,4 +171,83 @@ CONVOPS_API int effocr_convops_linear(int precision, int epilogue, const void* x
   if (epilogue == EPI_BIAS_SCALE_RESID) { g.resid = resid; g.ldr = n; g.scale = scale; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   return gemm2_supported(precision, n, k) ? gemm2_nt(precision, epilogue, g, s) : gemm_nt(precision, epilogue, g, s);
+}
+
+// ---- the ViT path (patch.hip, vit_ops.hip, qkvattn.hip, EPI_PATCH of gemm.hip / gemm2.hip; layouts: kernels.hpp).  Buffers in the
+// fragment-blocked layout must be addressable up to the next multiple of 32 rows.  A shape the launcher refuses keeps the launcher's own code.
+// patch.hip patch_embed_fused: every field of PatchArgs + prec (0 = bf16, 1 = f16); cls may be NULL (the class-token rows stay as they are)
+CONVOPS_API int effocr_convops_vit_patch_embed(int prec, const void* x, int x16, int B, int H, int W, const void* wb, const float* bias, const float* pos,
+                                               const float* cls, float* out, int D, int P, void* stream) {
+  convops_patch_dw = 0; convops_patch_grid = 0;
+  if (!x || !wb || !bias || !pos || !out) return fail(EFFOCR_EINVAL, "convops_vit_patch_embed: NULL argument");
+  if (B < 0 || H < 16 || W < 16 || D < 1 || P < 1) return fail(EFFOCR_EINVAL, "convops_vit_patch_embed: bad shape");
+  if ((int64_t)B * (P + 1) >= (int64_t)1 << 31 || (int64_t)B * 3 * H * W >= (int64_t)1 << 40) return fail(EFFOCR_EUNSUPPORTED, "convops_vit_patch_embed: batch too large");
+  PatchArgs a{};
+  a.x = x; a.B = B; a.H = H; a.W = W; a.x16 = x16 ? 1 : 0; a.Wb = wb; a.bias = bias; a.pos = pos; a.cls = cls; a.out = out; a.D = D; a.P = P;
+  return patch_embed_fused(prec, a, static_cast<hipStream_t>(stream));
+}
+// slice width (128 / 256 / 384) and grid of the calling thread's last effocr_convops_vit_patch_embed launch (0, 0: nothing was launched)
+CONVOPS_API void effocr_convops_vit_patch_embed_last_dispatch(int* dw, int* grid) {
+  if (dw) *dw = convops_patch_dw;
+  if (grid) *grid = convops_patch_grid;
+}
+// vit_ops.hip im2col_patch16: crops [B,3,H,W] (fp32, or with x16 already prec's 16-bit type) -> patch rows [B * (H/16) * (W/16)][768] in prec's type
+CONVOPS_API int effocr_convops_vit_im2col16(int prec, const void* x, int x16, int B, int H, int W, void* col, void* stream) {
+  if (!x || !col) return fail(EFFOCR_EINVAL, "convops_vit_im2col16: NULL argument");
+  if (B < 0 || H < 16 || W < 16) return fail(EFFOCR_EINVAL, "convops_vit_im2col16: bad shape");
+  return im2col_patch16(prec, x, x16 ? 1 : 0, B, H, W, col, static_cast<hipStream_t>(stream));
+}
+// EPI_PATCH dispatched as vit_forward does (api.hip): gemm2_nt where gemm2_supported(prec, D, 768), gemm_nt otherwise.  col [B * P][768] and w
+// [D][768] in prec's type, dense rows; fp32 out rows img * (P + 1) + 1 + p = acc + pos[1 + p] + bias, row-major [.][D] or (blk_out, gemm2 only)
+// fragment-blocked; the class-token rows are not written.
+CONVOPS_API int effocr_convops_vit_patch_gemm(int prec, const void* col, const void* w, const float* bias, const float* pos, float* out, int B, int P,
+                                              int D, int blk_out, void* stream) {
+  if (prec != PREC_BF16 && prec != PREC_FP16 && prec != PREC_FP32) return fail(EFFOCR_EINVAL, "convops_vit_patch_gemm: unknown precision");
+  if (!col || !w || !bias || !pos || !out) return fail(EFFOCR_EINVAL, "convops_vit_patch_gemm: NULL argument");
+  if (B < 0 || P < 1 || D < 1) return fail(EFFOCR_EINVAL, "convops_vit_patch_gemm: bad shape");
+  if ((int64_t)B * (P + 1) * std::max(D, 768) >= (int64_t)1 << 31) return fail(EFFOCR_EUNSUPPORTED, "convops_vit_patch_gemm: rows * max(D, 768) beyond 32-bit GEMM indices");
+  const bool g2 = gemm2_supported(prec, D, 768);
+  if (blk_out && !g2) return fail(EFFOCR_EUNSUPPORTED, "convops_vit_patch_gemm: only gemm2 (16-bit operands, D % 128 == 0) writes the fragment-blocked layout");
+  GemmArgs g{};
+  g.X = col; g.ldx = 768; g.W = w; g.ldw = 768; g.bias = bias; g.out = out; g.ldo = D; g.pos = pos; g.M = B * P; g.N = D; g.K = 768; g.P = P;
+  g.blk_out = blk_out ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return g2 ? gemm2_nt(prec, EPI_PATCH, g, s) : gemm_nt(prec, EPI_PATCH, g, s);
+}
+// vit_ops.hip set_cls_rows: row img * T of x [B * T][D] fp32 (row-major or blocked) = cls_pos0; status_zero (optional device int) is set to 0
+CONVOPS_API int effocr_convops_vit_set_cls(const float* cls_pos0, float* x, int B, int T, int D, int blocked, int* status_zero, void* stream) {
+  if (!cls_pos0 || !x) return fail(EFFOCR_EINVAL, "convops_vit_set_cls: NULL argument");
+  if (B < 0 || T < 1 || D < 4 || D % 4) return fail(EFFOCR_EINVAL, "convops_vit_set_cls: bad shape (D must be a multiple of 4)");
+  return set_cls_rows(cls_pos0, x, B, T, D, blocked ? 1 : 0, status_zero, static_cast<hipStream_t>(stream));
+}
+// vit_ops.hip gather_cls_rows_blocked: rows img * T of x (fp32 blocked) and att (16-bit blocked) -> rows img of xc / ac (blocked, B rows)
+CONVOPS_API int effocr_convops_vit_gather_cls(const float* x, const void* att, int B, int T, int D, float* xc, void* ac, void* stream) {
+  if (!x || !att || !xc || !ac) return fail(EFFOCR_EINVAL, "convops_vit_gather_cls: NULL argument");
+  if (B < 0 || T < 1 || D < 8 || D % 8) return fail(EFFOCR_EINVAL, "convops_vit_gather_cls: bad shape (D must be a multiple of 8)");
+  return gather_cls_rows_blocked(x, att, B, T, D, xc, ac, static_cast<hipStream_t>(stream));
+}
+// qkvattn.hip qkv_attn_fused: every field of QkvAttnArgs a caller sets (img0 is the launcher's) + prec
+CONVOPS_API int effocr_convops_vit_qkv_attn(int prec, const void* xn, const void* wb, const float* bias, void* out, int B, int T, int D, int64_t rows_alloc,
+                                            int cls_only, int hsplit, void* stream) {
+  convops_qa_launches = 0;
+  std::fill(&convops_qa_last[0][0], &convops_qa_last[0][0] + 12, 0);
+  if (!xn || !wb || !bias || !out) return fail(EFFOCR_EINVAL, "convops_vit_qkv_attn: NULL argument");
+  if (B < 0 || T < 1 || D < 1 || rows_alloc < 0 || hsplit < 0) return fail(EFFOCR_EINVAL, "convops_vit_qkv_attn: bad shape");
+  QkvAttnArgs a{};
+  a.xn = xn; a.Wb = wb; a.bias = bias; a.out = out; a.B = B; a.T = T; a.D = D; a.rows_alloc = rows_alloc; a.cls_only = cls_only ? 1 : 0; a.hsplit = hsplit;
+  return qkv_attn_fused(prec, a, static_cast<hipStream_t>(stream));
+}
+// launches of the calling thread's last effocr_convops_vit_qkv_attn (0 .. 2: the split tail of a batch is a second one); out6 (optional) takes
+// launch `which`: {D, token tiles, 1 = class-token form, P.V steps (13: short tail, 14), head split, grid}
+CONVOPS_API int effocr_convops_vit_qkv_attn_last_dispatch(int which, int* out6) {
+  if (out6 && which >= 0 && which < 2) std::copy(convops_qa_last[which], convops_qa_last[which] + 6, out6);
+  return convops_qa_launches;
+}
+// vit_ops.hip final_cls_norm: LayerNorm of row img * T of x (fp32, row-major or blocked) (+ F.normalize) -> emb [B][D]; status: optional device
+// int, ORed with 1 on a non-finite embedding
+CONVOPS_API int effocr_convops_vit_final_norm(const float* x, int B, int T, int D, const float* gamma, const float* beta, float eps, int l2norm,
+                                              int blocked, float* emb, int* status, void* stream) {
+  if (!x || !gamma || !beta || !emb) return fail(EFFOCR_EINVAL, "convops_vit_final_norm: NULL argument");
+  if (B < 0 || T < 1 || D < 1) return fail(EFFOCR_EINVAL, "convops_vit_final_norm: bad shape");
+  return final_cls_norm(x, B, T, D, gamma, beta, eps, l2norm ? 1 : 0, blocked ? 1 : 0, emb, status, static_cast<hipStream_t>(stream));
 }

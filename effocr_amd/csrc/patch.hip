@@ -29,6 +29,12 @@ constexpr int PE_SLABS16 = 4;                            // ... for 16-bit pixel
 #define PATCH_NT 1                                        // non-temporal: 1 = pixel loads (read once), 2 = row stores
 #endif
 namespace effocr {
+#ifdef EFFOCR_CONVOPS
+thread_local int convops_patch_dw = 0, convops_patch_grid = 0;   // the test-only library (convops_api.hip): slice width and grid of the calling thread's last launch
+#define PATCH_REC(dw, grid) (convops_patch_dw = (dw), convops_patch_grid = (int)(grid))
+#else
+#define PATCH_REC(dw, grid) ((void)0)
+#endif
 namespace {
 
 template <int I, int N, typename F> __device__ __forceinline__ void pfor(F&& f) {
@@ -221,15 +227,16 @@ int launch_patch(const PatchArgs& a, hipStream_t s) {
   // as three 128-wide slices — same arithmetic per output, the pixels of a panel are re-read out of the L2 — a third of the weight
   // stream and of the MFMAs per CU, on three times the CUs, while the slices still fit one round
   if (a.D == 384 && panels * 3 <= device_cus()) {
+    PATCH_REC(128, panels * 3);
     hipLaunchKernelGGL((patch_embed_kernel<E, X, 128>), dim3((unsigned)(panels * 3)), dim3(256), 0, s, a);
     return check_launch("patch_embed_fused");
   }
   const int nsl = a.D > 384 ? a.D / 384 : 1;              // 384-wide output slices of a panel (ViT-B: 2)
   const dim3 grid((unsigned)(panels * nsl)), blk(256);
   switch (a.D) {
-    case 128: hipLaunchKernelGGL((patch_embed_kernel<E, X, 128>), grid, blk, 0, s, a); break;
-    case 256: hipLaunchKernelGGL((patch_embed_kernel<E, X, 256>), grid, blk, 0, s, a); break;
-    case 384: case 768: hipLaunchKernelGGL((patch_embed_kernel<E, X, 384>), grid, blk, 0, s, a); break;
+    case 128: PATCH_REC(128, grid.x); hipLaunchKernelGGL((patch_embed_kernel<E, X, 128>), grid, blk, 0, s, a); break;
+    case 256: PATCH_REC(256, grid.x); hipLaunchKernelGGL((patch_embed_kernel<E, X, 256>), grid, blk, 0, s, a); break;
+    case 384: case 768: PATCH_REC(384, grid.x); hipLaunchKernelGGL((patch_embed_kernel<E, X, 384>), grid, blk, 0, s, a); break;
     default: return fail(EFFOCR_EUNSUPPORTED, "patch_embed_fused: embed dim must be 128, 256, 384 or 768");
   }
   return check_launch("patch_embed_fused");

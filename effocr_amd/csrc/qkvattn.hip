@@ -53,6 +53,16 @@
 #endif
 
 namespace effocr {
+#ifdef EFFOCR_CONVOPS
+// the test-only library (convops_api.hip): {D, token tiles, class-token form, P.V steps, head split, grid} of the calling thread's last
+// qkv_attn_fused call, one row per launch (the split tail is a second one)
+thread_local int convops_qa_launches = 0, convops_qa_last[2][6] = {};
+#define QA_REC(d, ntt, cls, npv) (convops_qa_launches < 2 ? (void)(convops_qa_last[convops_qa_launches][0] = (d), convops_qa_last[convops_qa_launches][1] = (ntt), \
+  convops_qa_last[convops_qa_launches][2] = (cls), convops_qa_last[convops_qa_launches][3] = (npv), convops_qa_last[convops_qa_launches][4] = hs, \
+  convops_qa_last[convops_qa_launches][5] = (int)grid.x) : (void)0, ++convops_qa_launches)
+#else
+#define QA_REC(d, ntt, cls, npv) ((void)0)
+#endif
 namespace {
 
 // -DQA_STAMP (tools/ab_build.sh variant, never shipped): every wave of every workgroup records s_memtime at the milestones of the head
@@ -651,13 +661,13 @@ int launch_qkvattn(const QkvAttnArgs& a, hipStream_t s) {
   const QkvAttnArgs& a2 = ah;
   const dim3 grid((unsigned)(hs > 1 ? nimg_launch * hs : (nimg_launch < cus ? nimg_launch : cus))), blk(256);
   const bool short_tail = a.T <= 32 * ntt - 16;          // the last 16 keys are all padding
-  if (a.D == 384 && ntt == 7 && a.cls_only && short_tail) hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7, true, 13>), grid, blk, 0, s, a2);
-  else if (a.D == 384 && ntt == 7 && a.cls_only) hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7, true>), grid, blk, 0, s, a2);
-  else if (a.D == 384 && ntt == 7 && short_tail) hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7, false, 13>), grid, blk, 0, s, a2);
-  else if (a.D == 384 && ntt == 7) hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7>), grid, blk, 0, s, a2);
-  else if (a.D == 384 && ntt <= 2) hipLaunchKernelGGL((qkvattn_kernel<E, 384, 2>), grid, blk, 0, s, a2);
-  else if (a.D == 128 && ntt == 7) hipLaunchKernelGGL((qkvattn_kernel<E, 128, 7>), grid, blk, 0, s, a2);
-  else if (a.D == 128 && ntt <= 2) hipLaunchKernelGGL((qkvattn_kernel<E, 128, 2>), grid, blk, 0, s, a2);
+  if (a.D == 384 && ntt == 7 && a.cls_only && short_tail) { QA_REC(384, 7, 1, 13); hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7, true, 13>), grid, blk, 0, s, a2); }
+  else if (a.D == 384 && ntt == 7 && a.cls_only) { QA_REC(384, 7, 1, 14); hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7, true>), grid, blk, 0, s, a2); }
+  else if (a.D == 384 && ntt == 7 && short_tail) { QA_REC(384, 7, 0, 13); hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7, false, 13>), grid, blk, 0, s, a2); }
+  else if (a.D == 384 && ntt == 7) { QA_REC(384, 7, 0, 14); hipLaunchKernelGGL((qkvattn_kernel<E, 384, 7>), grid, blk, 0, s, a2); }
+  else if (a.D == 384 && ntt <= 2) { QA_REC(384, 2, 0, 4); hipLaunchKernelGGL((qkvattn_kernel<E, 384, 2>), grid, blk, 0, s, a2); }
+  else if (a.D == 128 && ntt == 7) { QA_REC(128, 7, 0, 14); hipLaunchKernelGGL((qkvattn_kernel<E, 128, 7>), grid, blk, 0, s, a2); }
+  else if (a.D == 128 && ntt <= 2) { QA_REC(128, 2, 0, 4); hipLaunchKernelGGL((qkvattn_kernel<E, 128, 2>), grid, blk, 0, s, a2); }
   else return fail(EFFOCR_EUNSUPPORTED, "qkv_attn_fused: (embed dim, tokens) must be (128|384, <=64 or 193..224)");
   return check_launch("qkv_attn_fused");
 }

@@ -170,7 +170,8 @@ __global__ __launch_bounds__(256) void cls_norm_kernel(const float* __restrict__
     for (int i = 0; i < V; ++i)
 #pragma unroll
       for (int e = 0; e < 4; ++e) ss += y[i][e] * y[i][e];
-    const float nrm = fmaxf(sqrtf(group_sum<G>(ss)), 1e-12f);    // F.normalize: x / max(||x||, eps)
+    const float nr = sqrtf(group_sum<G>(ss));
+    const float nrm = nr < 1e-12f ? 1e-12f : nr;                 // F.normalize: x / max(||x||, eps); a NaN norm stays NaN, as torch's clamp_min
 #pragma unroll
     for (int i = 0; i < V; ++i)
 #pragma unroll

@@ -1,6 +1,7 @@
 """ctypes binding of effocr_amd/libeffocr_convops.so, the TEST-ONLY operator library (csrc/convops_api.hip): thin wrappers over the
-convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, the ConvNeXt launchers of convnext.hip and
-the linears of convnext_forward (gemm.hip, gemm2.hip).  `make` builds it next to the product
+convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, the ConvNeXt launchers of convnext.hip, the
+linears of convnext_forward (gemm.hip, gemm2.hip) and the non-GEMM launchers of the ViT path (patch.hip, vit_ops.hip, qkvattn.hip and
+EPI_PATCH of both GEMMs: effocr_convops_vit_*).  `make` builds it next to the product
 libraries (``__graft_entry__.build()``); a missing library is an error here — no skip, no fallback."""
 
 import ctypes
@@ -8,13 +9,13 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO_PATH = os.path.join(ROOT, "effocr_amd", "libeffocr_convops.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 PREC_BF16, PREC_FP16, PREC_FP32 = 0, 1, 2
 PREC = {"bf16": PREC_BF16, "fp16": PREC_FP16, "fp32": PREC_FP32}
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 
 _c = ctypes
-_vp, _i, _sz = _c.c_void_p, _c.c_int, _c.c_size_t
+_vp, _i, _sz, _i64, _f = _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int64, _c.c_float
 SIGNATURES = {
     "effocr_convops_abi_version": (_i, []),
     "effocr_convops_last_error": (_c.c_char_p, []),
@@ -41,6 +42,15 @@ SIGNATURES = {
     "effocr_convops_cnx_ln_s2d": (_i, [_i, _vp] + [_i] * 5 + [_vp] * 4),                   # prec, x, B, H, W, C, Cp, lnw, lnb, out
     "effocr_convops_cnx_head": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _i, _vp, _vp, _vp]),     # x, B, HW, C, Cp, lnw, lnb, l2norm, emb, status
     "effocr_convops_linear": (_i, [_i, _i] + [_vp] * 6 + [_i] * 3 + [_vp]),                # precision, epilogue, x, w, bias, resid, scale, out, m, n, k
+    "effocr_convops_vit_patch_embed": (_i, [_i, _vp] + [_i] * 4 + [_vp] * 5 + [_i, _i, _vp]),   # prec, x, x16, B, H, W, wb, bias, pos, cls, out, D, P
+    "effocr_convops_vit_patch_embed_last_dispatch": (None, [_c.POINTER(_i), _c.POINTER(_i)]),
+    "effocr_convops_vit_im2col16": (_i, [_i, _vp] + [_i] * 4 + [_vp, _vp]),                # prec, x, x16, B, H, W, col
+    "effocr_convops_vit_patch_gemm": (_i, [_i] + [_vp] * 5 + [_i] * 4 + [_vp]),            # prec, col, w, bias, pos, out, B, P, D, blk_out
+    "effocr_convops_vit_set_cls": (_i, [_vp, _vp] + [_i] * 4 + [_vp, _vp]),                # cls_pos0, x, B, T, D, blocked, status_zero
+    "effocr_convops_vit_gather_cls": (_i, [_vp, _vp] + [_i] * 3 + [_vp] * 3),              # x, att, B, T, D, xc, ac
+    "effocr_convops_vit_qkv_attn": (_i, [_i] + [_vp] * 4 + [_i] * 3 + [_i64, _i, _i, _vp]),   # prec, xn, wb, bias, out, B, T, D, rows_alloc, cls_only, hsplit
+    "effocr_convops_vit_qkv_attn_last_dispatch": (_i, [_i, _c.POINTER(_i)]),
+    "effocr_convops_vit_final_norm": (_i, [_vp] + [_i] * 3 + [_vp, _vp, _f, _i, _i, _vp, _vp, _vp]),   # x, B, T, D, gamma, beta, eps, l2norm, blocked, emb, status
 }
 EXPORTS = sorted(SIGNATURES)
 
@@ -70,6 +80,25 @@ def last_dispatch():
     nw, ks = _i(0), _i(0)
     lib().effocr_convops_last_dispatch(ctypes.byref(nw), ctypes.byref(ks))
     return nw.value, ks.value
+
+
+def patch_last_dispatch():
+    """(slice width, grid) of this thread's last effocr_convops_vit_patch_embed launch."""
+    dw, grid = _i(0), _i(0)
+    lib().effocr_convops_vit_patch_embed_last_dispatch(ctypes.byref(dw), ctypes.byref(grid))
+    return dw.value, grid.value
+
+
+def qkv_attn_last_dispatch():
+    """One (D, token tiles, class-token form, P.V steps, head split, grid) per launch of this thread's last effocr_convops_vit_qkv_attn."""
+    buf = (_i * 6)()
+    n = lib().effocr_convops_vit_qkv_attn_last_dispatch(0, buf)
+    out = []
+    for k in range(min(n, 2)):
+        lib().effocr_convops_vit_qkv_attn_last_dispatch(k, buf)
+        out.append(tuple(buf))
+    assert n == len(out), f"{n} launches recorded, room for 2"
+    return out
 
 
 def ptr(t):

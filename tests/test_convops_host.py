@@ -25,10 +25,10 @@ def test_library_loads_and_exports_every_wrapper():
     raw = ctypes.CDLL(CL.SO_PATH)
     for name in CL.EXPORTS:
         assert hasattr(raw, name), f"{name} is not exported"
-    assert len(CL.EXPORTS) == 22
+    assert len(CL.EXPORTS) == 31                           # 22 + the nine effocr_convops_vit_* of the ViT path
     out = subprocess.run(["nm", "-D", "--defined-only", CL.SO_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == CL.EXPORTS      # no other function leaves the library
-    assert CL.last_dispatch() == (0, 0)
+    assert CL.last_dispatch() == (0, 0) and CL.patch_last_dispatch() == (0, 0) and CL.qkv_attn_last_dispatch() == []
 
 
 def _conv2d(L, Cin=32, Cout=32, sl=(0, 0, 0, 0, 0, 0), relu=0, silu=0):

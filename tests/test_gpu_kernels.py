@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from effocr_amd import _lib
+from tests.vit_ops_ref import from_blocked, to_blocked
 
 pytestmark = pytest.mark.gpu
 
@@ -153,20 +154,6 @@ def test_unsupported_shapes_fail_loudly(ab_lib, dev):
 
 
 # ---------------------------------------------------------------- fragment-blocked fast-path operators (gemm3, blocked LN)
-def to_blocked(t, rows_alloc):
-    """[rows, cols] tensor -> flat buffer in the cell layout [rows_alloc/32][cols/ch][32][ch] (ch = 16 bytes)."""
-    rows, cols = t.shape
-    ch = 16 // t.element_size()
-    buf = torch.zeros((rows_alloc, cols), dtype=t.dtype)
-    buf[:rows] = t
-    return buf.view(rows_alloc // 32, 32, cols // ch, ch).permute(0, 2, 1, 3).contiguous().view(-1)
-
-
-def from_blocked(flat, rows, cols, rows_alloc):
-    ch = 16 // flat.element_size()
-    return flat.view(rows_alloc // 32, cols // ch, 32, ch).permute(0, 2, 1, 3).contiguous().view(rows_alloc, cols)[:rows]
-
-
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 @pytest.mark.parametrize("epi", ["bias", "bias_gelu", "bias_resid"])
 @pytest.mark.parametrize("shape", [(197 * 40, 384, 1536), (300, 192, 256), (1000, 768, 768), (70000, 256, 384), (1, 2304, 768), (33, 3072, 768), (70000, 768, 256), (140000, 192, 256)])
