@@ -497,6 +497,30 @@ def yolov8_lib():
     return _load_family(YOLOV8_SO_PATH, "yolov8", YOLOV8_ABI_VERSION, _yolov8_signatures(), "YOLOv8 localizer")
 
 
+# libeffocr_yolo11.so (include/effocr_yolo11.h): the YOLO11 localizers yolo11n / s / m / l / x (a builder, an attention kernel and a
+# depthwise 3x3 kernel of its own; the convolution, the YOLOv5 data-movement kernels and the YOLOv8 stem and decode compiled in again,
+# hidden) and the two op entry points its kernel tests call.  Letterbox and NMS stay the product library's.
+YOLO11_SO_PATH = os.path.join(_HERE, "libeffocr_yolo11.so")
+YOLO11_ABI_VERSION = 1     # == EFFOCR_YOLO11_ABI_VERSION of include/effocr_yolo11.h
+YOLO11_MAX_TOKENS = 1600   # == EFFOCR_YOLO11_MAX_TOKENS
+
+
+def _yolo11_signatures():
+    c = ctypes
+    vp, i32 = c.c_void_p, c.c_int
+    sig = {k.replace("effocr_yolov8_", "effocr_yolo11_"): v for k, v in _yolov8_signatures().items()}
+    sig["effocr_yolo11_op_attention"] = (i32, [vp, i32, i32, i32, i32, vp, vp])
+    sig["effocr_yolo11_op_dwconv3x3"] = (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp])
+    return sig
+
+
+YOLO11_EXPORTS = tuple(sorted(_yolo11_signatures()))
+
+
+def yolo11_lib():
+    return _load_family(YOLO11_SO_PATH, "yolo11", YOLO11_ABI_VERSION, _yolo11_signatures(), "YOLO11 localizer")
+
+
 head_check = _family_check("head")
 swin_check = _family_check("swin")
 resnet_check = _family_check("resnet")
@@ -506,6 +530,7 @@ beit_check = _family_check("beit")
 bit_check = _family_check("bit")
 vit8_check = _family_check("vit8")
 yolov8_check = _family_check("yolov8")
+yolo11_check = _family_check("yolo11")
 levit_check = _family_check("levit")
 regnet_check = _family_check("regnet")
 

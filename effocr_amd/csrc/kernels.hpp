@@ -230,6 +230,17 @@ int stem3x3s2_nchw(const float* x, const float* wt, int wt_ld, const float* bias
 int yolov8_decode(const float* box, int box_ld, const float* cls, int cls_ld, float* pred, int B, int ny, int nx, int nc, float stride, int64_t total,
                   int64_t row0, hipStream_t s);
 
+// yolo11.hip — the YOLO11 localizer's own kernels (libeffocr_yolo11.so only)
+constexpr int Y11_MAX_TOKENS = 1600;   // attention_nhwc: tokens per image (a 1280 x 1280 input); memory does not grow with it, the cap bounds what is tested
+// softmax(32^-1/2 q k^T) v per (image, head) over the N = H * W pixels: qkv NHWC fp32, channel qkv_off + head * 128 + (q 0..31 | k 32..63 | v 64..127)
+// of rows qkv_ld wide -> out channel out_off + head * 64 + d of rows out_ld wide.  fp32 throughout; key tiles of 64 with a running maximum
+// and sum; a query row's summation order depends on N alone
+int attention_nhwc(const float* qkv, int qkv_ld, int qkv_off, float* out, int out_ld, int out_off, int B, int N, int heads, hipStream_t s);
+// depthwise 3x3, stride 1, zero pad 1: in channel c of pixel p at in[p * in_ld + in_off + (icut ? c / icut * istride + c % icut : c)], w [C][9]
+// (tap ky * 3 + kx, BN folded), out = act(sum of the taps in ascending order + bias) (+ add), C % 4 == 0 and every offset / ld % 4 == 0
+int dwconv3x3_nhwc(const float* in, int in_ld, int in_off, int icut, int istride, const float* w, const float* bias, int silu, const float* add, int add_ld,
+                   int add_off, float* out, int out_ld, int out_off, int B, int H, int W, int C, hipStream_t s);
+
 // convnext.hip — the ConvNeXt encoder's own kernels (fp32 channels-last residual stream [tokens][Cp], Cp = channels padded to 128;
 // the pointwise linears are gemm_nt / gemm2_nt).  Every kernel computes a token from that token's inputs alone, in a fixed order.
 // stem: 4x4/s4 conv (wt: [48 taps (c, ky, kx)][128] fp32) + channel LayerNorm over C0 <= 128 -> x [B*(S/4)^2][128] (pad channels 0)

@@ -1,5 +1,5 @@
-// Host-side core of the YOLO localizer engines: localizer.hip (YOLOv5, in libeffocr_hip.so) and yolov8_api.hip (YOLOv8, in
-// libeffocr_yolov8.so) describe their networks with the same pieces — a table of named parameters, NHWC activation buffers, channel-slice
+// Host-side core of the YOLO localizer engines: localizer.hip (YOLOv5, in libeffocr_hip.so), yolov8_api.hip (YOLOv8, in
+// libeffocr_yolov8.so) and yolo11_api.hip (YOLO11, in libeffocr_yolo11.so) describe their networks with the same pieces — a table of named parameters, NHWC activation buffers, channel-slice
 // views of them and a flat list of ops — and share the weight layout, the BN folding / packing and the op loop of a forward.  What
 // differs between the two families stays in their own files: the layer table, the stem kernel and the Detect decode (the two hooks of
 // loc_run_ops).  No kernel and no device memory here.  Include it from ONE translation unit per shared library.
@@ -26,7 +26,9 @@ struct LParam { std::string name; std::vector<int64_t> shape; int64_t numel; std
 struct Buf { int H, W, C; };                             // NHWC activation buffer (per image)
 struct View { int buf, off, C, S = 0; };                 // channel slice of a buffer: C channels, S (0: = C) stored channels (C padded to 32)
 int stored(const View& v) { return v.S ? v.S : v.C; }
-enum { OP_STEM = 0, OP_CONV = 1, OP_UP = 2, OP_POOL = 3, OP_DETECT = 4 };
+enum { OP_STEM = 0, OP_CONV = 1, OP_UP = 2, OP_POOL = 3, OP_DETECT = 4,
+       OP_ATTN = 5,                                      // multi-head self-attention over the map's pixels (YOLO11's C2PSA): in = the qkv tensor, level = heads
+       OP_DW = 6 };                                      // depthwise 3x3, stride 1 (+ res: a tensor added behind the activation): conv = index into dws
 struct Op {
   int type;
   View in, out, res;                                     // res.buf < 0: no residual
@@ -37,7 +39,12 @@ struct LConv { std::string w, bn, bias; int cin, cout, cout_pad, k, stride, pad,
                std::string w2, bn2; int cout1 = 0;
                int cin_st = 0, icut = 0, ishift = 0;    // weight columns: cin_st stored input channels per tap; the input is segments of icut channels, each stored ishift channels wider: channel ci sits at ci + (ci / icut) * ishift
                int row2 = 0, cout2 = 0;                 // pair: the second block's cout2 rows start at weight row row2 (= cout1 unless padded)   // w2 / bn2: a second Conv block stacked behind the first cout1 output channels (C3's cv1 | cv2 in one launch)   // w16: the bf16 copy, rows padded to 64 k
+               int q16 = 0;                             // 1: bf16-rounded operands in the bf16_operands mode although the block has no activation (YOLO11's qkv / proj / ffn.1)
                int ocut = 0, oshift = 0; };             // one block whose output is segments of ocut channels, each stored oshift channels wider (0: one segment, padded at its end)
+
+// a depthwise 3x3 Conv block (Conv2d(groups = C, bias = False) + BN + optional SiLU): weights [cst][9] (tap ky * 3 + kx), BN folded; its
+// input channel ci is read at in.off + (ci / icut) * istride + ci % icut (icut = 0: at in.off + ci)
+struct LDw { std::string w, bn; int c, cst, act, icut, istride; size_t w_off, b_off; };
 
 // what both localizer handles are: the C handle structs derive from it
 struct LocNet {
@@ -47,6 +54,7 @@ struct LocNet {
   std::vector<Buf> bufs;
   std::vector<Op> ops;
   std::vector<LConv> convs;
+  std::vector<LDw> dws;
   int stem_col = -1;                                     // buffer of the stem's im2col rows
   size_t wbytes = 0;
   const char* wdev = nullptr;
@@ -101,6 +109,16 @@ struct Builder {
     e->convs.push_back(c);
     e->ops.push_back({OP_CONV, in, out, {-1, 0, 0}, (int)e->convs.size() - 1, 0});
   }
+  // ultralytics Conv / DWConv block `name` with k = 3, groups = channels: in -> out (+ res behind the activation).  icut / istride: LDw
+  void dwconv(const std::string& name, View in, View out, int act, View res = {-1, 0, 0}, int icut = 0, int istride = 0) {
+    LDw d; d.w = name + ".conv.weight"; d.bn = name + ".bn"; d.c = out.C; d.cst = stored(out); d.act = act; d.icut = icut; d.istride = istride; d.w_off = d.b_off = 0;
+    ladd(e, d.w, {out.C, 1, 3, 3});
+    ladd(e, name + ".bn.weight", {out.C}); ladd(e, name + ".bn.bias", {out.C}); ladd(e, name + ".bn.running_mean", {out.C}); ladd(e, name + ".bn.running_var", {out.C});
+    e->dws.push_back(d);
+    e->ops.push_back({OP_DW, in, out, res, (int)e->dws.size() - 1, 0});
+  }
+  // softmax(scale q k^T) v per head over the pixels of `in` = [heads x (q 32 | k 32 | v 64)] channels -> out = heads x 64 channels
+  void attention(View in, View out, int heads) { e->ops.push_back({OP_ATTN, in, out, {-1, 0, 0}, -1, heads}); }
   // the stem Conv(3, c, k, 2, pad): OP_STEM, its im2col rows (kpad wide) only on the direct_stem = 0 path
   void stem(const std::string& name, View out, int k, int pad, int kpad, int H1, int W1) {
     e->stem_col = new_buf(H1, W1, kpad);
@@ -122,6 +140,10 @@ void layout_weights(LocNet* e) {
     c.w16_off = off; off = align_up(off + (size_t)c.cout_pad * ((K + 63) / 64 * 64) * 2, 256);
     c.wt_off = 0;
     if (c.kpad) { c.wt_off = off; off = align_up(off + (size_t)c.k * c.k * c.cin_st * c.cout_pad * 4, 256); }   // stem: [tap][channel] transpose (scalar-weight kernel)
+  }
+  for (auto& d : e->dws) {
+    d.w_off = off; off = align_up(off + (size_t)d.cst * 9 * 4, 256);
+    d.b_off = off; off = align_up(off + (size_t)d.cst * 4, 256);
   }
   e->wbytes = off;
 }
@@ -178,6 +200,25 @@ void pack_convs(const LocNet* e, std::vector<char>& blob) {
         }
         w16[(size_t)co * Kp64 + kk] = (uint16_t)u;
       }
+  }
+}
+
+// depthwise blocks: BN folded as above, fp32 only; stored channels past c are zero rows with a zero bias (SiLU(0) = 0)
+void pack_dws(const LocNet* e, std::vector<char>& blob) {
+  for (const LDw& d : e->dws) {
+    float* wd = reinterpret_cast<float*>(blob.data() + d.w_off);
+    float* bd = reinterpret_cast<float*>(blob.data() + d.b_off);
+    const auto& w = LP(e, d.w);
+    for (int ch = 0; ch < d.cst; ++ch) {
+      bd[ch] = 0.f;
+      for (int t = 0; t < 9; ++t) wd[(size_t)ch * 9 + t] = 0.f;
+      if (ch >= d.c) continue;
+      const double g = LP(e, d.bn + ".weight")[ch], bt = LP(e, d.bn + ".bias")[ch], mu = LP(e, d.bn + ".running_mean")[ch],
+                   var = LP(e, d.bn + ".running_var")[ch];
+      const double sc = g / sqrt(var + 1e-3);
+      bd[ch] = (float)(bt - mu * sc);
+      for (int t = 0; t < 9; ++t) wd[(size_t)ch * 9 + t] = (float)((double)w[(size_t)ch * 9 + t] * sc);
+    }
   }
 }
 
@@ -243,10 +284,11 @@ int loc_set_option(const std::string& what, LocNet* loc, const char* name, int v
 }
 
 // One forward: the ops in order.  direct_stem(conv, out view, out pointer) runs the family's own stem kernel and returns 1 when it did, 0
-// when the shape is not its (then, as with direct_stem = 0, im2col + the 1x1 implicit GEMM), < 0 on an error; detect(op, P) decodes a level.
-template <typename Stem, typename Detect>
+// when the shape is not its (then, as with direct_stem = 0, im2col + the 1x1 implicit GEMM), < 0 on an error; detect(op, P) decodes a level;
+// extra(op, P) runs the op kinds whose kernels only some libraries have (OP_ATTN, OP_DW).
+template <typename Stem, typename Detect, typename Extra>
 int loc_run_ops(const std::string& what, const LocNet* loc, const float* x_dev, int batch, float* pred_dev, void* workspace_dev, size_t workspace_bytes,
-                hipStream_t s, Stem direct_stem, Detect detect) {
+                hipStream_t s, Stem direct_stem, Detect detect, Extra extra) {
   if (!loc) return fail(EFFOCR_EINVAL, what + "_forward: NULL localizer");
   if (batch < 0) return fail(EFFOCR_EINVAL, what + "_forward: negative batch");
   if (batch == 0) return EFFOCR_OK;
@@ -286,7 +328,7 @@ int loc_run_ops(const std::string& what, const LocNet* loc, const float* x_dev, 
         if (op.res.buf >= 0) { a.resid = P(op.res.buf); a.res_ld = loc->bufs[op.res.buf].C; a.res_off = op.res.off; }
         a.B = batch; a.H = i.H; a.W = i.W; a.Cin = c.cin_st; a.Cout = c.cout_pad; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
         a.OH = o.H; a.OW = o.W; a.silu = c.act;
-        if (loc->bf16 && c.act) a.w16 = loc->wdev + c.w16_off;
+        if (loc->bf16 && (c.act || c.q16)) a.w16 = loc->wdev + c.w16_off;
         a.partial = loc->call_size_invariant ? nullptr : reinterpret_cast<float*>(ws + w.split); a.partial_bytes = LOC_SPLIT_BYTES;
         if ((rc = conv2d_nhwc(a, s))) return rc;
         break;
@@ -305,9 +347,20 @@ int loc_run_ops(const std::string& what, const LocNet* loc, const float* x_dev, 
         if ((rc = detect(op, P))) return rc;
         break;
       }
+      default: {
+        if ((rc = extra(op, P))) return rc;
+        break;
+      }
     }
   }
   return EFFOCR_OK;
+}
+// the networks made of the five op kinds above alone (YOLOv5, YOLOv8)
+template <typename Stem, typename Detect>
+int loc_run_ops(const std::string& what, const LocNet* loc, const float* x_dev, int batch, float* pred_dev, void* workspace_dev, size_t workspace_bytes,
+                hipStream_t s, Stem direct_stem, Detect detect) {
+  auto none = [&](const Op&, auto&) { return fail(EFFOCR_EINVAL, what + "_forward: an op kind this library has no kernel for"); };
+  return loc_run_ops(what, loc, x_dev, batch, pred_dev, workspace_dev, workspace_bytes, s, direct_stem, detect, none);
 }
 
 }  // namespace

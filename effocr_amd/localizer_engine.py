@@ -297,6 +297,169 @@ def yolov8_scale(state_dict):
     return scale
 
 
+# ultralytics YOLO11 scales (yolo11.yaml `scales`): (depth_multiple, width_multiple, max_channels).  Written from the published yaml,
+# nn/modules and parse_model without an ultralytics install at hand: UNVERIFIED against a real checkpoint (DESIGN.md section 3 "YOLO11");
+# the tables give the five published parameter counts (tests/test_yolo11_host.py).
+YOLO11_SCALES = {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)}
+YOLO11_DFL_KEY = "model.23.dfl.conv.weight"
+# init_yolo11_state_dict: the gains of the q / k rows (per PSABlock) and of the v rows of attn.qkv over the kaiming bound.  Found by
+# measurement on the test inputs (tests/test_yolo11_host.py holds the result): the q / k gains give logits whose spread about each
+# query's mean is about 1; the v gain of the one-block scales makes the attention branch large against the block's input, without
+# which a wrong softmax hardly reaches the predictions (the stride-32 tokens of a small input are near copies of each other)
+YOLO11_QK_GAIN = {"n": (67.3,), "s": (70.2,), "m": (57.9,), "l": (64.5, 2.4), "x": (48.5, 2.3)}
+YOLO11_V_GAIN = {"n": 16.0, "s": 16.0, "m": 16.0, "l": 1.0, "x": 1.0}
+YOLO11_CLS_GAIN = 8.0    # ... and of the last class convolution
+
+
+def _yolo11_dims(scale):
+    """(channels(c), repeats of a "2" row, c3k forced) of parse_model at ``scale``."""
+    if scale not in YOLO11_SCALES:
+        raise ValueError(f"unknown YOLO11 scale {scale!r} (one of {', '.join(YOLO11_SCALES)})")
+    depth, width, max_channels = YOLO11_SCALES[scale]
+    return (lambda c: math.ceil(min(c, max_channels) * width / 8) * 8), max(round(2 * depth), 1), scale in "mlx"
+
+
+def yolo11_param_shapes(nc, scale="n"):
+    """{ultralytics key: shape} of YOLO11<scale> (yolo11.yaml, ``scale`` in "nsmlx") with ``nc`` classes, in module order."""
+    ch, n2, force_c3k = _yolo11_dims(scale)
+    shapes = {}
+
+    def conv(name, c1, c2, k, groups=1):
+        shapes[name + ".conv.weight"] = (c2, c1 // groups, k, k)
+        for s in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"{name}.bn.{s}"] = (c2,)
+
+    def c3k(name, c):
+        c_ = c // 2
+        conv(name + ".cv1", c, c_, 1)
+        conv(name + ".cv2", c, c_, 1)
+        conv(name + ".cv3", 2 * c_, c, 1)
+        for i in range(2):
+            conv(f"{name}.m.{i}.cv1", c_, c_, 3)
+            conv(f"{name}.m.{i}.cv2", c_, c_, 3)
+
+    def c3k2(name, c1, c2, is_c3k, e=0.5):
+        c = int(c2 * e)
+        conv(name + ".cv1", c1, 2 * c, 1)
+        conv(name + ".cv2", (2 + n2) * c, c2, 1)
+        for i in range(n2):
+            if is_c3k or force_c3k:
+                c3k(f"{name}.m.{i}", c)
+            else:
+                conv(f"{name}.m.{i}.cv1", c, c // 2, 3)
+                conv(f"{name}.m.{i}.cv2", c // 2, c, 3)
+
+    def c2psa(name, c1):
+        c = c1 // 2
+        conv(name + ".cv1", c1, 2 * c, 1)
+        conv(name + ".cv2", 2 * c, c1, 1)
+        for j in range(n2):
+            conv(f"{name}.m.{j}.attn.qkv", c, 2 * c, 1)
+            conv(f"{name}.m.{j}.attn.proj", c, c, 1)
+            conv(f"{name}.m.{j}.attn.pe", c, c, 3, groups=c)
+            conv(f"{name}.m.{j}.ffn.0", c, 2 * c, 1)
+            conv(f"{name}.m.{j}.ffn.1", 2 * c, c, 1)
+
+    c64, c128, c256, c512, c1024 = ch(64), ch(128), ch(256), ch(512), ch(1024)
+    conv("model.0", 3, c64, 3)
+    conv("model.1", c64, c128, 3)
+    c3k2("model.2", c128, c256, False, 0.25)
+    conv("model.3", c256, c256, 3)
+    c3k2("model.4", c256, c512, False, 0.25)
+    conv("model.5", c512, c512, 3)
+    c3k2("model.6", c512, c512, True)
+    conv("model.7", c512, c1024, 3)
+    c3k2("model.8", c1024, c1024, True)
+    conv("model.9.cv1", c1024, c1024 // 2, 1)
+    conv("model.9.cv2", c1024 // 2 * 4, c1024, 1)
+    c2psa("model.10", c1024)
+    c3k2("model.13", c1024 + c512, c512, False)
+    c3k2("model.16", c512 + c512, c256, False)
+    conv("model.17", c256, c256, 3)
+    c3k2("model.19", c256 + c512, c512, False)
+    conv("model.20", c512, c512, 3)
+    c3k2("model.22", c512 + c1024, c1024, True)
+    feats = (c256, c512, c1024)
+    c2, c3 = max(16, c256 // 4, 4 * YOLOV8_REG_MAX), max(c256, min(nc, 100))
+    for l, cin in enumerate(feats):
+        conv(f"model.23.cv2.{l}.0", cin, c2, 3)
+        conv(f"model.23.cv2.{l}.1", c2, c2, 3)
+        shapes[f"model.23.cv2.{l}.2.weight"] = (4 * YOLOV8_REG_MAX, c2, 1, 1)
+        shapes[f"model.23.cv2.{l}.2.bias"] = (4 * YOLOV8_REG_MAX,)
+    for l, cin in enumerate(feats):
+        conv(f"model.23.cv3.{l}.0.0", cin, cin, 3, groups=cin)
+        conv(f"model.23.cv3.{l}.0.1", cin, c3, 1)
+        conv(f"model.23.cv3.{l}.1.0", c3, c3, 3, groups=c3)
+        conv(f"model.23.cv3.{l}.1.1", c3, c3, 1)
+        shapes[f"model.23.cv3.{l}.2.weight"] = (nc, c3, 1, 1)
+        shapes[f"model.23.cv3.{l}.2.bias"] = (nc,)
+    shapes[YOLO11_DFL_KEY] = (1, YOLOV8_REG_MAX, 1, 1)
+    return shapes
+
+
+def init_yolo11_state_dict(nc=2, scale="n", seed=0):
+    """Seeded random YOLO11<scale> weights: as ``init_yolov8_state_dict`` (kaiming-uniform convolutions, BatchNorm statistics drawn the
+    same way, Detect.bias_init, the DFL constant, 32 x the gain on the last box convolution), with two more gains.  ``YOLO11_QK_GAIN[scale][block]`` x
+    the kaiming bound on the q and k rows of every attn.qkv and ``YOLO11_V_GAIN[scale]`` x on its v rows: the attention logits
+    32^-1/2 q . k then have a standard deviation of order 1 about each query's mean (tests/test_yolo11_host.py measures it), so the softmax
+    is neither uniform nor one-hot, and a mistake in it moves the predictions.  ``YOLO11_CLS_GAIN`` x on the last class convolution: the
+    class logits then spread around the very negative bias instead of sitting on it, where the sigmoid hides every change."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, shp in yolo11_param_shapes(nc, scale).items():
+        if k == YOLO11_DFL_KEY:
+            sd[k] = torch.arange(YOLOV8_REG_MAX, dtype=torch.float32).view(shp)
+        elif k.endswith(".weight") and len(shp) == 4:
+            fan_in = shp[1] * shp[2] * shp[3]
+            gain = 32.0 if k.startswith("model.23.cv2.") and k.endswith(".2.weight") else YOLO11_CLS_GAIN if k.startswith("model.23.cv3.") and k.endswith(".2.weight") else 1.0
+            sd[k] = (torch.rand(shp, generator=g) * 2 - 1) * (math.sqrt(3.0 / fan_in) * 1.2 * gain)
+            if ".attn.qkv." in k:                              # rows per head: q 32 | k 32 | v 64
+                sd[k].view(-1, 128, *shp[1:])[:, :64] *= YOLO11_QK_GAIN[scale][int(k.split(".")[3])]
+                sd[k].view(-1, 128, *shp[1:])[:, 64:] *= YOLO11_V_GAIN[scale]
+        elif k.endswith("bn.weight"):
+            sd[k] = 1.0 + 0.2 * torch.randn(shp, generator=g)
+        elif k.endswith("bn.bias") or k.endswith("running_mean"):
+            sd[k] = 0.1 * torch.randn(shp, generator=g)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(shp, generator=g)
+        elif k.endswith(".bias"):                              # Detect.bias_init
+            l = int(k.split(".")[3])
+            b = 0.05 * torch.randn(shp, generator=g)
+            sd[k] = b + (1.0 if ".cv2." in k else math.log(5 / nc / (640 / STRIDES[l]) ** 2))
+    return sd
+
+
+def yolo11_scale(state_dict):
+    """The scale ("n" | "s" | "m" | "l" | "x") of an ultralytics YOLO11 detection state dict: width from the stem's output channels
+    (``model.0.conv.weight``), depth from the number of blocks in ``model.2.m`` (what tells m from l), the cap from the width of
+    ``model.7``; every key and shape must then match that scale's table, and the DFL tensor must be the constant 0 .. 15.  ValueError
+    names the first mismatches."""
+    for key in (YOLO11_DFL_KEY, "model.23.cv3.0.2.bias", "model.0.conv.weight", "model.7.conv.weight"):
+        if key not in state_dict:
+            raise ValueError(f"state dict has no '{key}': not an ultralytics YOLO11 detection model")
+    nc = int(state_dict["model.23.cv3.0.2.bias"].numel())
+    c0 = int(state_dict["model.0.conv.weight"].shape[0])
+    nm = len({k.split(".")[3] for k in state_dict if k.startswith("model.2.m.")})
+    by_width = [s for s in YOLO11_SCALES if _yolo11_dims(s)[0](64) == c0]
+    if not by_width:
+        raise ValueError(f"model.0.conv.weight has {c0} output channels: no YOLO11 scale has that width "
+                         f"({', '.join(f'{s}: {_yolo11_dims(s)[0](64)}' for s in YOLO11_SCALES)})")
+    by_depth = [s for s in by_width if _yolo11_dims(s)[1] == nm]
+    if not by_depth:
+        raise ValueError(f"model.2.m has {nm} blocks, but a stem of {c0} channels is YOLO11{'/'.join(by_width)} with "
+                         f"{' / '.join(str(_yolo11_dims(s)[1]) for s in by_width)}")
+    scale = by_depth[0]
+    bad = _shape_mismatches(state_dict, yolo11_param_shapes(nc, scale))
+    if bad:
+        c7, want7 = int(state_dict["model.7.conv.weight"].shape[0]), _yolo11_dims(scale)[0](1024)
+        cap = f" (model.7 is {c7} wide, yolo11{scale} caps it at {want7}: another max_channels)" if c7 != want7 else ""
+        raise ValueError(f"state dict does not match yolo11{scale}{cap}: " + "; ".join(bad[:6]) + (f" (+{len(bad) - 6} more)" if len(bad) > 6 else ""))
+    dfl = state_dict[YOLO11_DFL_KEY].detach().to("cpu", torch.float32).reshape(-1)
+    if not torch.equal(dfl, torch.arange(YOLOV8_REG_MAX, dtype=torch.float32)):
+        raise ValueError(f"{YOLO11_DFL_KEY} is not the constant 0 .. {YOLOV8_REG_MAX - 1}: the decode has that projection built in")
+    return scale
+
+
 def _load_state_dict(model_path):
     if isinstance(model_path, dict):
         sd = model_path
@@ -497,14 +660,32 @@ class HipLocalizerV8(HipLocalizer):
         return int(state_dict["model.22.cv3.0.2.bias"].numel()), scale, "yolov8" + scale
 
 
+class HipLocalizerV11(HipLocalizer):
+    """Device-resident YOLO11 (n / s / m / l / x): the network is libeffocr_yolo11.so's (include/effocr_yolo11.h); its rows are YOLOv8's
+    — (cx, cy, w, h, 1.0, class scores) — so ``letterbox``, ``nms_async`` and ``nms_batch_async`` are HipLocalizer's, on the product
+    library.  An input of more than 1600 stride-32 pixels (above 1280 x 1280) is refused by the library."""
+
+    _PREFIX = "effocr_yolo11"
+
+    def _network_library(self):
+        return _lib.yolo11_lib(), _lib.yolo11_check
+
+    @staticmethod
+    def _identify(state_dict, arch):
+        scale = yolo11_scale(state_dict)
+        if arch is not None and arch != "yolo11" + scale:
+            raise ValueError(f"arch={arch!r}, but the state dict is yolo11{scale}")
+        return int(state_dict["model.23.cv3.0.2.bias"].numel()), scale, "yolo11" + scale
+
+
 class EffLocalizer:
 
     def __init__(self, model_path, iou_thresh=0.01, conf_thresh=0.30, vertical=False, num_cores=None, providers=None,
                  input_shape=(640, 640), model_backend='yolo', device=None, precision="fp32", arch=None, call_size_invariant=False):
         # precision (extension): "fp32" = fp32 MFMA operands (the oracle's arithmetic), "bf16" = bf16-rounded operands for every
         # convolution with an activation, fp32 accumulation and fp32 Detect heads (2-3x the network throughput)
-        # arch (extension): "yolov5n" ... "yolov5x", "yolov8n" ... "yolov8x" or None; family and scale are read from the state dict (a
-        # model.22.dfl.conv.weight key: YOLOv8) and must agree
+        # arch (extension): "yolov5n" ... "yolov5x", "yolov8n" ... "yolov8x", "yolo11n" ... "yolo11x" or None; family and scale are read
+        # from the state dict (a model.23.dfl.conv.weight key: YOLO11, a model.22.dfl.conv.weight key: YOLOv8) and must agree
         # num_cores / providers are ORT knobs (localizer_engine.py:17-23): accepted and ignored.
         if model_backend != 'yolo':
             raise NotImplementedError('Backend {} is not implemented'.format(model_backend))
@@ -513,7 +694,7 @@ class EffLocalizer:
         self._input_shape = (int(input_shape[0]), int(input_shape[1]))
         self._model_backend = model_backend
         sd = _load_state_dict(model_path)
-        engine = HipLocalizerV8 if YOLOV8_DFL_KEY in sd else HipLocalizer      # the checkpoint says which network it is
+        engine = HipLocalizerV11 if YOLO11_DFL_KEY in sd else HipLocalizerV8 if YOLOV8_DFL_KEY in sd else HipLocalizer   # the checkpoint says which network it is
         self._eng_net = engine(sd, input_shape=self._input_shape, device=device, precision=precision, arch=arch,
                                call_size_invariant=call_size_invariant)
 
