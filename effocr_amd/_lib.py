@@ -487,6 +487,9 @@ def _yolov8_signatures():
         "num_outputs": (i32, [vp]),
         "workspace_bytes": (sz, [vp, i32]),
         "forward": (i32, [vp, vp, i32, vp, vp, sz, vp]),
+        # the two op entry points tests/test_gpu_localizer_ops.py calls (libeffocr_yolo11.so has none for these kernels)
+        "op_decode": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, c.c_float, i64, i64, vp]),
+        "op_stem": (i32, [vp, vp, i32, vp, vp] + [i32] * 9 + [vp]),
     }.items()}
 
 
@@ -508,7 +511,7 @@ YOLO11_MAX_TOKENS = 1600   # == EFFOCR_YOLO11_MAX_TOKENS
 def _yolo11_signatures():
     c = ctypes
     vp, i32 = c.c_void_p, c.c_int
-    sig = {k.replace("effocr_yolov8_", "effocr_yolo11_"): v for k, v in _yolov8_signatures().items()}
+    sig = {k.replace("effocr_yolov8_", "effocr_yolo11_"): v for k, v in _yolov8_signatures().items() if "_op_" not in k}
     sig["effocr_yolo11_op_attention"] = (i32, [vp, i32, i32, i32, i32, vp, vp])
     sig["effocr_yolo11_op_dwconv3x3"] = (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp])
     return sig

@@ -9,7 +9,9 @@
 //                         by size / 640 in float64 and rounded again (Python's round(): half to even; the literal 640 of :315-318), resolved
 //                         like the numpy slice im[y0:y1, x0:x1] (negative bounds count from the end, clipped to [0, size]) and widened to
 //                         the full line height (width when vertical) -> int32 [total, 5] = (x0, y0, x1, y1, line), total
-// A bitonic network over (key, row) pairs in LDS: the row index as the second sort key makes it stable; NaN keys rank last (torch.sort).
+// A bitonic network over (key, row) pairs in LDS: the row index as the second sort key makes it stable; NaN keys rank last (torch.sort),
+// and the network's padding entries (max_det .. P) carry NaN keys and the largest rows, so they rank behind those too: with +inf keys
+// they ranked in front of a NaN-keyed row and pushed it out of the first max_det entries, whose place a row past the line's end took.
 #include "../../include/effocr_hip.h"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -41,9 +43,9 @@ __global__ __launch_bounds__(256) void boxes_sort_kernel(const float* __restrict
   __syncthreads();
   int mine = 0;
   for (int j = tid; j < P; j += 256) {
-    float k = INFINITY;
+    float k = j < max_det ? INFINITY : NAN;
     if (j < cnt && r[j * 6 + 5] == 0.0f) { k = r[j * 6 + axis]; ++mine; }
-    key[j] = k; idx[j] = j;                                // (rows past max_det: padding of the network, +inf, behind everything by index)
+    key[j] = k; idx[j] = j;                                // (rows past max_det: padding of the network, NaN: behind every row, a NaN key's too, by index)
   }
   if (mine) atomicAdd(&nch, mine);
   __syncthreads();

@@ -2,7 +2,8 @@
 // convolution, pooling and data-movement launchers of resnet.hip, resnet16.hip and yolo.hip, over the ConvNeXt launchers of convnext.hip,
 // over the linears of convnext_forward (gemm.hip, gemm2.hip) and over the non-GEMM launchers of the ViT path (patch.hip, vit_ops.hip,
 // qkvattn.hip: effocr_convops_vit_*), which this library compiles once more with hidden visibility, so that tests/test_gpu_convops.py,
-// tests/test_gpu_convnext_ops.py and tests/test_gpu_vit_ops.py compare each kernel on its own with a float64 reference.  No product library
+// tests/test_gpu_convnext_ops.py, tests/test_gpu_vit_ops.py and (yolo.hip's Detect decode) tests/test_gpu_localizer_ops.py compare each
+// kernel on its own with a float64 reference.  No product library
 // exports these and no product code loads this one: libeffocr_hip.so is at its size cap (DESIGN.md "Library split").
 // All device pointers are caller-owned, `stream` is a hipStream_t (NULL = the default stream); every call returns 0 or a negative
 // EFFOCR_E* code (include/effocr_hip.h) whose message effocr_convops_last_error() holds for the calling thread.
@@ -14,7 +15,7 @@
 #include <string>
 
 #define CONVOPS_API extern "C" __attribute__((visibility("default")))
-#define EFFOCR_CONVOPS_ABI_VERSION 3
+#define EFFOCR_CONVOPS_ABI_VERSION 4
 
 namespace effocr {
 
@@ -250,4 +251,14 @@ CONVOPS_API int effocr_convops_vit_final_norm(const float* x, int B, int T, int 
   if (!x || !gamma || !beta || !emb) return fail(EFFOCR_EINVAL, "convops_vit_final_norm: NULL argument");
   if (B < 0 || T < 1 || D < 1) return fail(EFFOCR_EINVAL, "convops_vit_final_norm: bad shape");
   return final_cls_norm(x, B, T, D, gamma, beta, eps, l2norm ? 1 : 0, blocked ? 1 : 0, emb, status, static_cast<hipStream_t>(stream));
+}
+
+// ---- the YOLOv5 Detect decode (yolo.hip yolo_decode): raw [B * ny * nx][raw_ld] (channel an * no + o) -> rows row0 .. row0 + na * ny * nx
+// of pred [B][total][no]; anchors_px: the level's na (w, h) pairs in input pixels, on the HOST.  na != 3 keeps the launcher's own code.
+CONVOPS_API int effocr_convops_yolo_decode(const float* raw, int raw_ld, float* pred, int B, int ny, int nx, int na, int no, float stride,
+                                           const float* anchors_px, int64_t total, int64_t row0, void* stream) {
+  if (!raw || !pred || !anchors_px) return fail(EFFOCR_EINVAL, "convops_yolo_decode: NULL argument");
+  if (B < 0 || ny < 1 || nx < 1 || na < 1 || no < 5 || (int64_t)raw_ld < (int64_t)na * no) return fail(EFFOCR_EINVAL, "convops_yolo_decode: bad shape");
+  if (total < 1 || row0 < 0 || row0 + (int64_t)na * ny * nx > total) return fail(EFFOCR_EINVAL, "convops_yolo_decode: the level's rows do not fit the prediction tensor");
+  return yolo_decode(raw, raw_ld, pred, B, ny, nx, na, no, stride, anchors_px, total, row0, static_cast<hipStream_t>(stream));
 }

@@ -189,3 +189,22 @@ YOLOV8_API int effocr_yolov8_forward(effocr_yolov8_t* loc, const float* x_dev, i
   };
   return loc_run_ops("yolov8", loc, x_dev, batch, pred_dev, workspace_dev, workspace_bytes, s, stem, detect);
 }
+
+// ---------------------------------------------------------------- test entry points: one kernel each, caller-made tensors
+// yolov8.hip yolov8_decode: box [B * ny * nx][box_ld] (64 logits: 4 sides x 16 bins), cls [B * ny * nx][cls_ld] (nc logits) -> rows row0 ..
+// row0 + ny * nx of pred [B][total][5 + nc]
+YOLOV8_API int effocr_yolov8_op_decode(const float* box_dev, int box_ld, const float* cls_dev, int cls_ld, float* pred_dev, int batch, int ny, int nx, int nc,
+                                       float stride, int64_t total, int64_t row0, void* stream) {
+  if (!box_dev || !cls_dev || !pred_dev) return fail(EFFOCR_EINVAL, "yolov8_op_decode: NULL argument");
+  if (batch < 0 || ny < 1 || nx < 1 || nc < 1 || box_ld < 64 || cls_ld < nc || total < 1 || row0 < 0) return fail(EFFOCR_EINVAL, "yolov8_op_decode: bad shape");
+  return yolov8_decode(box_dev, box_ld, cls_dev, cls_ld, pred_dev, batch, ny, nx, nc, stride, total, row0, LS(stream));
+}
+// yolov8.hip stem3x3s2_nchw: x [B][3][H][W], wt [27 taps (ky, kx, c)][wt_ld], bias [cout_st] (zero from cout on) -> channels out_off ..
+// out_off + cout_st of out [B * OH * OW][out_ld], the channels from cout on 0
+YOLOV8_API int effocr_yolov8_op_stem(const float* x_dev, const float* wt_dev, int wt_ld, const float* bias_dev, float* out_dev, int batch, int H, int W, int OH,
+                                     int OW, int out_ld, int out_off, int cout, int cout_st, void* stream) {
+  if (!x_dev || !wt_dev || !bias_dev || !out_dev) return fail(EFFOCR_EINVAL, "yolov8_op_stem: NULL argument");
+  if (batch < 0 || H < 1 || W < 1 || OH < 1 || OW < 1 || wt_ld < 1 || wt_ld % 4 || out_ld < 1 || out_off < 0 || cout < 1 || cout_st < 1)
+    return fail(EFFOCR_EINVAL, "yolov8_op_stem: bad shape");
+  return stem3x3s2_nchw(x_dev, wt_dev, wt_ld, bias_dev, out_dev, batch, H, W, OH, OW, out_ld, out_off, cout, cout_st, LS(stream));
+}

@@ -81,6 +81,20 @@ size_t effocr_yolov8_workspace_bytes(const effocr_yolov8_t* loc, int batch);   /
 int effocr_yolov8_forward(effocr_yolov8_t* loc, const float* x_dev, int batch, float* pred_dev, void* workspace_dev, size_t workspace_bytes,
                           void* stream);
 
+/* ---- test entry points: one kernel each on caller-made device tensors (tests/test_gpu_localizer_ops.py); no handle, nothing of
+ * forward's state.  libeffocr_yolo11.so runs the same two kernels and has no entry points of its own for them.
+ *
+ * Detect decode of one level: box_dev [batch * ny * nx][box_ld] (the first 64 floats of a row: left, top, right, bottom x 16 bin
+ * logits; box_ld >= 64, a multiple of 4), cls_dev [batch * ny * nx][cls_ld] (nc class logits, cls_ld >= nc) -> rows row0 .. row0 + ny * nx
+ * of pred_dev [batch][total][5 + nc] = (cx, cy, w, h) * stride, 1.0f, sigmoid class scores; no other row is touched. */
+int effocr_yolov8_op_decode(const float* box_dev, int box_ld, const float* cls_dev, int cls_ld, float* pred_dev, int batch, int ny, int nx, int nc,
+                            float stride, int64_t total, int64_t row0, void* stream);
+/* The 3x3 / stride 2 / pad 1 stem + SiLU: x_dev [batch][3][H][W], wt_dev [27][wt_ld] (row (ky * 3 + kx) * 3 + c, wt_ld >= cout_st, a
+ * multiple of 4), bias_dev [cout_st] (0 from cout on) -> channels out_off .. out_off + cout_st of out_dev [batch * OH * OW][out_ld], the
+ * channels cout .. cout_st exactly 0.  OH = ceil(H / 2), OW = ceil(W / 2) a multiple of 4; cout, cout_st multiples of 16. */
+int effocr_yolov8_op_stem(const float* x_dev, const float* wt_dev, int wt_ld, const float* bias_dev, float* out_dev, int batch, int H, int W, int OH,
+                          int OW, int out_ld, int out_off, int cout, int cout_st, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO_PATH = os.path.join(ROOT, "effocr_amd", "libeffocr_convops.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 PREC_BF16, PREC_FP16, PREC_FP32 = 0, 1, 2
 PREC = {"bf16": PREC_BF16, "fp16": PREC_FP16, "fp32": PREC_FP32}
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
@@ -34,6 +34,8 @@ SIGNATURES = {
     "effocr_convops_stem6x6s2_g16": (_i, [_vp, _vp, _i, _vp, _vp] + [_i] * 9 + [_vp]),     # x, wt, wt_ld, bias, out, B, H, W, OH, OW, out_ld, out_off, cout, cout_st
     "effocr_convops_upsample2x": (_i, [_vp, _i, _i, _vp, _i, _i] + [_i] * 4 + [_vp]),      # in, in_ld, in_off, out, out_ld, out_off, B, H, W, C
     "effocr_convops_maxpool5": (_i, [_vp, _i, _i, _vp, _i, _i] + [_i] * 4 + [_vp]),
+    # raw, raw_ld, pred, B, ny, nx, na, no, stride, anchors_px (HOST, 2 * na floats), total, row0
+    "effocr_convops_yolo_decode": (_i, [_vp, _i, _vp] + [_i] * 5 + [_f, _c.POINTER(_f), _i64, _i64, _vp]),
     "effocr_convops_im2col16": (_i, [_i, _vp, _vp] + [_i] * 5 + [_vp]),                    # prec, x, col, B, H, W, OH, OW
     "effocr_convops_maxpool16": (_i, [_i, _vp, _vp] + [_i] * 6 + [_vp]),                   # prec, in, out, B, H, W, C, OH, OW
     "effocr_convops_avgpool16": (_i, [_i, _vp, _vp] + [_i] * 4 + [_vp, _vp]),              # prec, in, emb, B, HW, C, l2norm, status

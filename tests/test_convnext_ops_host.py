@@ -211,7 +211,7 @@ def test_chain_is_the_network():
 # ---------------------------------------------------------------------------------------------------- the entry points refuse before a launch
 def test_refusals_before_any_launch():
     L = CL.lib()
-    assert L.effocr_convops_abi_version() == CL.ABI_VERSION == 3
+    assert L.effocr_convops_abi_version() == CL.ABI_VERSION == 4
     stem = lambda S_, C0, x=DUMMY: L.effocr_convops_cnx_stem(x, 1, S_, DUMMY, DUMMY, DUMMY, DUMMY, C0, DUMMY, None)
     for S_, C0 in R.STEM_REFUSALS:
         assert stem(S_, C0) == CL.EUNSUPPORTED and "cnx_stem" in CL.last_error(), (S_, C0)

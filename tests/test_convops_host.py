@@ -25,7 +25,7 @@ def test_library_loads_and_exports_every_wrapper():
     raw = ctypes.CDLL(CL.SO_PATH)
     for name in CL.EXPORTS:
         assert hasattr(raw, name), f"{name} is not exported"
-    assert len(CL.EXPORTS) == 31                           # 22 + the nine effocr_convops_vit_* of the ViT path
+    assert len(CL.EXPORTS) == 32                           # 22 + the nine effocr_convops_vit_* of the ViT path + effocr_convops_yolo_decode
     out = subprocess.run(["nm", "-D", "--defined-only", CL.SO_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == CL.EXPORTS      # no other function leaves the library
     assert CL.last_dispatch() == (0, 0) and CL.patch_last_dispatch() == (0, 0) and CL.qkv_attn_last_dispatch() == []

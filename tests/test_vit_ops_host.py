@@ -189,7 +189,7 @@ def test_every_listed_mutant_is_rejected_somewhere():
 # ---------------------------------------------------------------------------------------------------- the entry points refuse before a launch
 def test_refusals_before_any_launch():
     L = CL.lib()
-    assert L.effocr_convops_abi_version() == CL.ABI_VERSION == 3
+    assert L.effocr_convops_abi_version() == CL.ABI_VERSION == 4
     pe = lambda prec=0, x=DUMMY, H=32, W=32, D=384, P=4, B=1: L.effocr_convops_vit_patch_embed(prec, x, 0, B, H, W, DUMMY, DUMMY, DUMMY, None, DUMMY, D, P, None)
     assert pe(x=None) == CL.EINVAL and pe(B=-1) == CL.EINVAL and "vit_patch_embed" in CL.last_error()
     assert pe(prec=2) == CL.EUNSUPPORTED and pe(D=512) == CL.EUNSUPPORTED and pe(H=40) == CL.EINVAL and pe(P=5) == CL.EINVAL
