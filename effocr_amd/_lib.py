@@ -461,6 +461,31 @@ def regnet_lib():
     return _load_family(REGNET_SO_PATH, "regnet", REGNET_ABI_VERSION, _regnet_signatures(), "RegNet encoder")
 
 
+# libeffocr_pvt.so (include/effocr_pvt.h): the PVTv2 encoders pvt_v2_b0 ... pvt_v2_b5 (attention over at most 49 spatially reduced keys, a
+# depthwise 3x3 + GELU on token rows, overlapping patch embeddings and the reduction as implicit GEMMs, a GEMM for its narrow widths).
+PVT_SO_PATH = os.path.join(_HERE, "libeffocr_pvt.so")
+PVT_ABI_VERSION = 1     # == EFFOCR_PVT_ABI_VERSION of include/effocr_pvt.h
+
+
+def _pvt_signatures():
+    c = ctypes
+    vp, i32 = c.c_void_p, c.c_int
+    sig = _encoder_signatures("pvt")
+    sig["effocr_pvt_reset_status"] = (i32, [vp, vp, vp])
+    sig["effocr_pvt_op_attention"] = (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp])      # test entry points
+    sig["effocr_pvt_op_dwconv_gelu"] = (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp])
+    sig["effocr_pvt_op_stem"] = (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp])
+    sig["effocr_pvt_op_conv_ln"] = (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp])
+    return sig
+
+
+PVT_EXPORTS = tuple(sorted(_pvt_signatures()))
+
+
+def pvt_lib():
+    return _load_family(PVT_SO_PATH, "pvt", PVT_ABI_VERSION, _pvt_signatures(), "PVTv2 encoder")
+
+
 # libeffocr_yolov8.so (include/effocr_yolov8.h): the YOLOv8 localizers yolov8n / s / m / l / x (a builder, a 3x3 stem and a distribution
 # decode of its own; it carries its own copies of the implicit-GEMM convolution and of the YOLOv5 engine's data-movement kernels, hidden).
 # Letterbox and NMS stay the product library's.
@@ -536,6 +561,7 @@ yolov8_check = _family_check("yolov8")
 yolo11_check = _family_check("yolo11")
 levit_check = _family_check("levit")
 regnet_check = _family_check("regnet")
+pvt_check = _family_check("pvt")
 
 
 def check(rc, what="", handle=None):

@@ -455,19 +455,32 @@ class RegNetEncoder(_FamilyEncoder):
         self._status_call("reset_status")
 
 
+class PvtEncoder(_FamilyEncoder):
+    """libeffocr_pvt.so: pvt_v2_b0 ... pvt_v2_b5 (and the miniatures pvt_v2_mini32_test / pvt_v2_mini64_test) at any img_size that is a
+    multiple of 32 from 32 to 224 — (img_size / 4)^2 tokens in the first stage, 3136 at 224^2, halved per side by every later stage, all
+    attending to (img_size / 32)^2 <= 49 reduced keys (the stem reads the fp32 crops and rounds to the operand type).  The checkpoint does
+    not fix the crop size.  Default sub-batch: a workspace under 1 GB, at most 256 crops."""
+    _family, _label = "pvt", "PVTv2"
+
+    def reset_status(self):
+        """Clear the current stream's status word without reading it (asynchronous)."""
+        self._status_call("reset_status")
+
+
 def make_encoder(arch, state_dict, img_size=224, precision=DEFAULT_PRECISION, device=None, call_size_invariant=False):
     """The engine of ``arch``: SwinEncoder (libeffocr_swin.so) for Swin, ResNetEncoder (libeffocr_resnet.so) for resnet34 / resnet50,
     MobileNetV3Encoder (libeffocr_mnv3.so) for mobilenetv3_small_075 / _small_100 / _large_100, EfficientNetEncoder
     (libeffocr_effnet.so) for efficientnet_b0 / tf_efficientnet_b0, BeitEncoder (libeffocr_beit.so) for beit_base_patch16_224 /
     beitv2_base_patch16_224, BitEncoder (libeffocr_bit.so) for resnetv2_50x1_bitm / resnetv2_101x1_bitm, Vit8Encoder (libeffocr_vit8.so) for
     vit_small_patch8_224 / vit_base_patch8_224, LevitEncoder (libeffocr_levit.so) for levit_128s / levit_128 / levit_192 / levit_256 /
-    levit_384, RegNetEncoder (libeffocr_regnet.so) for regnetx_002 ... regnetx_016 and regnety_002 ... regnety_016, HipEncoder
-    (libeffocr_hip.so) for every other architecture
+    levit_384, RegNetEncoder (libeffocr_regnet.so) for regnetx_002 ... regnetx_016 and regnety_002 ... regnety_016, PvtEncoder
+    (libeffocr_pvt.so) for pvt_v2_b0 ... pvt_v2_b5, HipEncoder (libeffocr_hip.so) for every other architecture
     (mobilenetv3_small_050 among them).  ``call_size_invariant``: HipEncoder's mode of that name; the other engines have the property
     in every mode and ignore the keyword."""
     cls = (SwinEncoder if W.is_swin(arch) else ResNetEncoder if W.is_resnet_lib(arch) else MobileNetV3Encoder if W.is_mnv3_lib(arch)
            else EfficientNetEncoder if W.is_efficientnet(arch) else BeitEncoder if W.is_beit(arch) else BitEncoder if W.is_bit(arch)
-           else Vit8Encoder if W.is_vit8(arch) else LevitEncoder if W.is_levit(arch) else RegNetEncoder if W.is_regnet(arch) else HipEncoder)
+           else Vit8Encoder if W.is_vit8(arch) else LevitEncoder if W.is_levit(arch) else RegNetEncoder if W.is_regnet(arch)
+           else PvtEncoder if W.is_pvt(arch) else HipEncoder)
     return cls(arch, state_dict, img_size=img_size, precision=precision, device=device, call_size_invariant=call_size_invariant)
 
 
@@ -482,7 +495,9 @@ def AutoEncoderFactory(backend, modelpath, precision=DEFAULT_PRECISION, img_size
     ``vit_small_patch8_224`` and ``vit_base_patch8_224`` (the fine-patch ViTs: 785 tokens per 224^2 crop),
     ``levit_128s``, ``levit_128``, ``levit_192``, ``levit_256`` and ``levit_384`` (the cheap transformers: 0.3 to 2.4 GMAC per 224^2 crop),
     ``regnetx_002``, ``regnetx_004``, ``regnetx_006``, ``regnetx_008``, ``regnetx_016``, ``regnety_002``, ``regnety_004``, ``regnety_006``,
-    ``regnety_008`` and ``regnety_016`` (the design-space CNNs with a grouped 3x3 per block: 0.2 to 1.6 GMAC per 224^2 crop)
+    ``regnety_008`` and ``regnety_016`` (the design-space CNNs with a grouped 3x3 per block: 0.2 to 1.6 GMAC per 224^2 crop),
+    ``pvt_v2_b0``, ``pvt_v2_b1``, ``pvt_v2_b2``, ``pvt_v2_b3``, ``pvt_v2_b4`` and ``pvt_v2_b5`` (the hierarchical transformers with spatially
+    reduced keys: 0.57 GFLOP per 224^2 crop for b0, 2.1 for b1)
     (the "hf" branch and XcitDinoEncoder are out
     of scope); anything else raises NotImplementedError exactly like the reference's ``else`` branch
     (encoders.py:93-95).

@@ -193,6 +193,24 @@ REGNET_MINI = {
 }
 REGNET_STEM = 32
 REGNET_BN_EPS = 1e-5
+PVT_CFG = {
+    # name: (stage widths, heads, depths, mlp ratios) — timm pvt_v2.py (the key names are written from memory of that file, not verified
+    # against a timm install; the architecture and the parameter counts are pinned to transformers.PvtV2Model): four stages, each an
+    # overlapping patch embedding (7x7/4 on the crop, then 3x3/2) + LayerNorm, pre-norm blocks whose keys and values come from a
+    # stride-sr convolution + LayerNorm of the tokens (sr = 8, 4, 2, 1) and whose MLP has a depthwise 3x3 + GELU, and a LayerNorm; the
+    # embedding is the mean of the last stage's tokens.  They run on libeffocr_pvt.so.  pvt_v2_b2_li and PVT v1 are not supported.
+    "pvt_v2_b0": ((32, 64, 160, 256), (1, 2, 5, 8), (2, 2, 2, 2), (8, 8, 4, 4)),
+    "pvt_v2_b1": ((64, 128, 320, 512), (1, 2, 5, 8), (2, 2, 2, 2), (8, 8, 4, 4)),
+    "pvt_v2_b2": ((64, 128, 320, 512), (1, 2, 5, 8), (3, 4, 6, 3), (8, 8, 4, 4)),
+    "pvt_v2_b3": ((64, 128, 320, 512), (1, 2, 5, 8), (3, 4, 18, 3), (8, 8, 4, 4)),
+    "pvt_v2_b4": ((64, 128, 320, 512), (1, 2, 5, 8), (3, 8, 27, 3), (8, 8, 4, 4)),
+    "pvt_v2_b5": ((64, 128, 320, 512), (1, 2, 5, 8), (3, 6, 40, 3), (4, 4, 4, 4)),
+    "pvt_v2_mini32_test": ((32, 64, 96, 128), (1, 2, 3, 4), (1, 1, 1, 1), (8, 8, 4, 4)),     # miniatures used only by fast tests: head width 32 ...
+    "pvt_v2_mini64_test": ((64, 128, 192, 256), (1, 2, 3, 4), (1, 1, 2, 1), (8, 8, 4, 4)),   # ... and 64
+}
+PVT_SUPPORTED = ("pvt_v2_b0", "pvt_v2_b1", "pvt_v2_b2", "pvt_v2_b3", "pvt_v2_b4", "pvt_v2_b5")
+PVT_SR = (8, 4, 2, 1)                 # spatial-reduction ratio per stage
+PVT_EPS = 1e-6
 MOBILENETV3_FEATURES = 1024           # conv_head width of MobileNetV3-Small (not scaled by the multiplier)
 MOBILENETV3_LARGE_FEATURES = 1280     # ... and of MobileNetV3-Large
 PATCH = 16
@@ -316,8 +334,11 @@ def embed_dim(arch):
         return LEVIT_CFG[arch][0][-1]
     if is_regnet(arch):
         return regnet_arch(arch)[0][-1]
+    if arch in PVT_CFG:
+        return PVT_CFG[arch][0][-1]
     _refuse_levit(arch)
     _refuse_regnet(arch)
+    _refuse_pvt(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -326,6 +347,17 @@ def _refuse_levit(arch):
     if isinstance(arch, str) and arch.startswith("levit"):
         raise NotImplementedError(f"unsupported LeViT {arch!r} (supported: {', '.join(LEVIT_SUPPORTED)}; levit_conv_*, levit_384_s8 and "
                                   "levit_512* are not)")
+
+
+def _refuse_pvt(arch):
+    """A PVT name this package does not build: NotImplementedError that lists the ones it does."""
+    if isinstance(arch, str) and arch.startswith("pvt"):
+        raise NotImplementedError(f"unsupported PVT {arch!r} (supported: {', '.join(PVT_SUPPORTED)}; pvt_v2_b2_li and PVT v1 are not)")
+
+
+def is_pvt(arch):
+    """pvt_v2_b0 ... pvt_v2_b5 (and the two miniatures): the encoders that run on libeffocr_pvt.so."""
+    return arch in PVT_CFG
 
 
 def is_levit(arch):
@@ -462,7 +494,9 @@ HEAD_KEYS = {"resnet": ("fc.weight", "fc.bias"), "vit": ("head.weight", "head.bi
              # (head_shapes lists all twelve keys, levit_fold_heads folds them into one matrix)
              "levit": ("head.linear.weight", "head.linear.bias"),
              # regnetx_* / regnety_*: the global average pool of the last block (final_conv is the identity)
-             "regnet": ("head.fc.weight", "head.fc.bias")}
+             "regnet": ("head.fc.weight", "head.fc.bias"),
+             # pvt_v2_*: the mean of the last stage's normalised tokens
+             "pvt": ("head.weight", "head.bias")}
 
 
 def _family(arch):
@@ -488,8 +522,11 @@ def _family(arch):
         return "levit"
     if is_regnet(arch):
         return "regnet"
+    if arch in PVT_CFG:
+        return "pvt"
     _refuse_levit(arch)
     _refuse_regnet(arch)
+    _refuse_pvt(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
 
 
@@ -629,9 +666,51 @@ def param_shapes(arch, img_size=224, num_classes=0):
         return _levit_shapes(arch, img_size)
     if is_regnet(arch):
         return _regnet_shapes(arch)
+    if arch in PVT_CFG:
+        return _pvt_shapes(arch)
     _refuse_levit(arch)
     _refuse_regnet(arch)
+    _refuse_pvt(arch)
     raise NotImplementedError(f"unsupported encoder architecture {arch!r}")
+
+
+def _pvt_shapes(arch):
+    """timm's state-dict order for a PyramidVisionTransformerV2 (pvt_v2.py; the key names are written from memory of that file, not
+    verified against a timm install): the stem's patch embedding, then per stage its downsample (stages 1 to 3), its blocks and its
+    norm.  Stage 3 has no attn.sr / attn.norm (reduction ratio 1).  The shapes do not depend on the crop size."""
+    widths, heads, depths, ratios = PVT_CFG[arch]
+    s = OrderedDict()
+
+    def wb(p, *shape):
+        s[p + ".weight"] = tuple(shape)
+        s[p + ".bias"] = (shape[0],)
+    wb("patch_embed.proj", widths[0], 3, 7, 7)
+    wb("patch_embed.norm", widths[0])
+    for i, (C, d, r, sr) in enumerate(zip(widths, depths, ratios, PVT_SR)):
+        p = f"stages.{i}."
+        if i > 0:
+            wb(p + "downsample.proj", C, widths[i - 1], 3, 3)
+            wb(p + "downsample.norm", C)
+        for j in range(d):
+            q = p + f"blocks.{j}."
+            wb(q + "norm1", C)
+            wb(q + "attn.q", C, C)
+            wb(q + "attn.kv", 2 * C, C)
+            wb(q + "attn.proj", C, C)
+            if sr > 1:
+                wb(q + "attn.sr", C, C, sr, sr)
+                wb(q + "attn.norm", C)
+            wb(q + "norm2", C)
+            wb(q + "mlp.fc1", r * C, C)
+            wb(q + "mlp.dwconv", r * C, 1, 3, 3)
+            wb(q + "mlp.fc2", C, r * C)
+        wb(p + "norm", C)
+    return s
+
+
+def pvt_num_learnable(arch, num_classes=0):
+    """Learnable parameters of the table, with an optional classifier."""
+    return sum(math.prod(shp) for shp in param_shapes(arch, 224, num_classes).values())
 
 
 def _regnet_shapes(arch):
@@ -996,6 +1075,8 @@ def init_state_dict(arch, seed=0, img_size=224, scale="unit", num_classes=0):
         return _init_levit(arch, seed, img_size, scale)
     if is_regnet(arch):
         return _init_regnet(arch, seed, scale)
+    if arch in PVT_CFG:
+        return _init_pvt(arch, seed, scale)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sd = OrderedDict()
@@ -1326,6 +1407,42 @@ def _init_regnet(arch, seed, scale):
     return sd
 
 
+def _init_pvt(arch, seed, scale):
+    """PVTv2 seeded init from a CPU Philox generator of its own.  scale="timm": trunc_normal(0.02) linears, convolutions N(0, 2 / fan_out)
+    (fan_out = k^2 Cout / groups), LayerNorms at identity, zero biases — what timm's initialiser gives.  scale="unit" (default):
+    fan-in-scaled linears and convolutions (a depthwise 3x3 has fan-in 9), LayerNorm gains U(0.5, 1.5), biases N(0, 0.1): attention over the
+    reduced keys is far from uniform and no term of the forward is switched off.  scale="trained": the unit rule with attn.proj and mlp.fc2
+    at a quarter of the fan-in scale, so that a block adds a fraction of the residual stream, as a trained network's does, instead of
+    doubling its variance."""
+    if scale not in ("unit", "timm", "trained"):
+        raise ValueError(f"scale must be 'unit', 'timm' or 'trained', got {scale!r}")
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 0x9E3779B1 + 0x70767432) % (1 << 63))
+    sd = OrderedDict()
+
+    def randn(shape, std):
+        return torch.randn(shape, generator=g, dtype=torch.float32) * std
+
+    for k, shp in _pvt_shapes(arch).items():
+        leaf = k.rsplit(".", 1)[-1]
+        is_ln = "norm" in k.rsplit(".", 2)[-2]
+        if scale == "timm":
+            if len(shp) == 1:
+                v = torch.ones(shp) if (leaf == "weight" and is_ln) else torch.zeros(shp)
+            elif len(shp) == 4:
+                groups = shp[0] if shp[1] == 1 and ".dwconv." in k else 1
+                v = randn(shp, math.sqrt(2.0 / (shp[2] * shp[3] * shp[0] / groups)))
+            else:
+                v = randn(shp, 0.02).clamp_(-0.04, 0.04)
+        elif len(shp) == 1:
+            v = torch.rand(shp, generator=g, dtype=torch.float32) + 0.5 if (leaf == "weight" and is_ln) else randn(shp, 0.1)
+        else:
+            gain = 0.25 if (scale == "trained" and (".attn.proj." in k or ".mlp.fc2." in k)) else 1.0
+            v = randn(shp, gain / math.sqrt(math.prod(shp[1:])))
+        sd[k] = v.contiguous()
+    return sd
+
+
 def _init_resnet(arch, seed, img_size, scale):
     """resnet34 / resnet50 from a CPU Philox generator of their own (resnet18 keeps the generic stream of init_state_dict).
     Convolutions are kaiming-normal (std sqrt(2 / fan_in)), as timm's.  scale="timm": BN at identity, with the last BN of every residual
@@ -1409,6 +1526,9 @@ def strip_prefix(sd, prefix="net."):
         sd = OrderedDict((k[len(prefix):], v) for k, v in sd.items())
     if "layers.0.blocks.0.attn.relative_position_bias_table" in sd:
         return swin_canonical(sd)
+    if any(".mlp.dwconv.dwconv." in k for k in sd):
+        # PVTv2: the original repository wraps the depthwise convolution in a module of its own (mlp.dwconv.dwconv.*)
+        return OrderedDict((k.replace(".mlp.dwconv.dwconv.", ".mlp.dwconv."), v) for k, v in sd.items())
     if "blocks.0.attn.relative_position_bias_table" in sd:
         # BEiT: the derived buffers of older timm checkpoints are dropped (the kernels compute the index from the geometry; k_bias is zeros)
         return OrderedDict((k, v) for k, v in sd.items() if not k.endswith((".attn.relative_position_index", ".attn.k_bias")))
@@ -1518,9 +1638,37 @@ def _infer_regnet(sd):
     raise ValueError(f"unsupported RegNet: {kind}, widths {widths}, depths {depths}, group width {gw} ({supported})")
 
 
+def _infer_pvt(sd):
+    """The PVTv2 a checkpoint holds: C0 and the depths pick the name, then every shape must match.  Pooled "linear" attention (attn.pool),
+    PVT v1 (position embeddings; no reduction in the overlapping form) and anything else is a ValueError that lists the supported names."""
+    supported = "supported: " + ", ".join(PVT_SUPPORTED)
+    if any(".attn.pool." in k for k in sd):
+        raise ValueError(f"unsupported PVT: pooled linear attention (pvt_v2_b2_li: attn.pool keys) ({supported})")
+    if any(k.startswith("pos_embed") or ".pos_embed" in k or k.startswith("cls_token") for k in sd):
+        raise ValueError(f"unsupported PVT: position embeddings (PVT v1) ({supported})")
+    pw = sd.get("patch_embed.proj.weight")
+    if "stages.0.blocks.0.attn.sr.weight" not in sd or pw is None or pw.dim() != 4 or tuple(pw.shape[1:]) != (3, 7, 7):
+        raise ValueError(f"unsupported PVT: no stage-0 spatial reduction (attn.sr) behind a 7x7 patch embedding ({supported})")
+    c0 = int(pw.shape[0])
+    depths = tuple(1 + max((int(k.split(".")[3]) for k in sd if k.startswith(f"stages.{i}.blocks.")), default=-1) for i in range(4))
+    first_bad = None
+    for name, (widths, _, dep, _) in PVT_CFG.items():
+        if widths[0] != c0 or dep != depths:
+            continue
+        bad = [k for k, shp in _pvt_shapes(name).items() if k not in sd or tuple(sd[k].shape) != shp]
+        if not bad:
+            return name
+        first_bad = first_bad or (name, bad[0])
+    if first_bad:
+        raise ValueError(f"unsupported PVT: stem width {c0} and depths {depths} are {first_bad[0]}'s, but {first_bad[1]} does not fit it ({supported})")
+    raise ValueError(f"unsupported PVT: stem width {c0}, depths {depths} ({supported})")
+
+
 def infer_arch(sd):
     """Guess the architecture of a checkpoint from its parameter shapes."""
     sd = strip_prefix(sd)
+    if any(k in sd for k in ("stages.0.blocks.0.attn.sr.weight", "stages.0.blocks.0.attn.kv.weight", "stages.0.blocks.0.attn.pool.weight")):
+        return _infer_pvt(sd)                              # PVTv2 (before the pos_embed branch: a PVT with position embeddings is refused there)
     if "stem.conv1.linear.weight" in sd or "patch_embed.0.c.weight" in sd:
         # LeViT: the shapes at the checkpoint's own crop size name the model
         supported = "supported: " + ", ".join(LEVIT_SUPPORTED) + " in timm >= 0.9's key layout"
